@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- Mcells/s of the fused Wright-EOS + steric pass on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+line.  ``--full`` adds everything else listed below (the other variants and precisions, the
+probes, the CPU baselines and the parity checks against the oracle).  ``--dump-outputs DIR``
+writes what the timed path returned in its last timed step as DIR/<name>.npy (float64): the
+per-step masso / eta / expansion_coeff and the scalars of the global epilogue.
 
 Workload (N=1): BASELINE.json configs[2], the roofline config -- OM4 0.25-degree synthetic
 grid 1440x1080x75, 120 time steps, fp64, global steric -- with theta/S (2 x 112 GB) resident
@@ -18,7 +24,7 @@ on 360x540 tiles, 279.9 GB of the card's 288 GiB), walked in 5 time chunks: K1 p
 asynchronous RCCL all-reduce of the chunk's masso(t) (+ volo, masso0, sum(area) in the first)
 overlapping the next chunk's kernel; value = all ranks' cells / max-over-ranks time.
 
-Besides the contract fields the JSON line carries
+Besides the contract fields the JSON line carries (all but roofline with --full only)
   roofline     -- K1 (k_steric_global): 16 algorithmic bytes per cell x cells per launch /
                   mean launch duration (HIP events on the launch stream, inside the timed
                   region) against the 8 TB/s HBM3E peak;
@@ -78,7 +84,30 @@ def parse():
                          "collective forced; timed beside the plain N=1 step, no extras")
     ap.add_argument("--input-dtype", choices=["f64", "f32"], default="f64",
                     help="storage type of theta/S (f32 = BASELINE.json configs[4]; the headline is f64)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras, the CPU baselines, the parity checks and the VALU probe "
+                         "(off: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(out, dirname):
+    """The arrays and scalars one timed step returned (parallel.finalize's dict: masso, eta,
+    expansion_coeff per time step, the global scalars) as ``dirname/<name>.npy`` in float64 --
+    a few KB, so nothing is sampled."""
+    os.makedirs(dirname, exist_ok=True)
+    written = []
+    for name, value in out.items():
+        arr = np.asarray(value.detach().cpu().numpy() if torch.is_tensor(value) else value)
+        if arr.dtype.kind not in "fiub":
+            continue
+        np.save(os.path.join(dirname, f"{name}.npy"), arr.astype(np.float64))
+        written.append(name)
+    return sorted(written)
 
 
 def kernel_source_sha():
@@ -270,8 +299,9 @@ def compact_line(line, detail_bytes):
     if "valu_roofline" in line:
         out["f64_fma_probe_lane_instr_per_s"] = line["valu_roofline"].get(
             "f64_fma_probe_lane_instr_per_s")
-    out["detail"] = (f"the line before this one (prefix BENCH_DETAIL, {detail_bytes} bytes) holds "
-                     "every row in full: kernel names, notes, checks, the non-default float32 modes")
+    if detail_bytes is not None:  # (a plain run prints no detail line)
+        out["detail"] = (f"the line before this one (prefix BENCH_DETAIL, {detail_bytes} bytes) holds "
+                         "every row in full: kernel names, notes, checks, the non-default float32 modes")
     return out
 
 
@@ -508,6 +538,8 @@ def main():
     rank, world, local_rank = parallel.init_from_env()
     if world != a.gpus:
         a.gpus = world
+    if not a.full:  # the headline only: no extras, no CPU legs, no VALU probe
+        a.no_extras, a.cpu_seconds = True, 0.0
     core.require_device()
     import torch.distributed as dist
 
@@ -640,6 +672,8 @@ def main():
         }
     if world > 1:
         elapsed = float(allreduce_scalar(elapsed, dist.ReduceOp.MAX, torch.float64))
+    if a.dump_outputs and rank == 0:  # the epilogue is replicated: rank 0's results are the job's
+        dump_outputs(out, a.dump_outputs)
 
     k1_kernel = _lib.last_kernel()  # the instantiation the timed region's last K1 call launched
     cells_rank = nt * nz * th * tw
@@ -721,7 +755,7 @@ def main():
         line.update(extras)
         if beside is not None:
             line["forced_collective"] = beside
-        add_valu_roofline(line, measure_valu_probe(dev) if world == 1 else None)
+        add_valu_roofline(line, measure_valu_probe(dev) if world == 1 and a.full else None)
         if extras:
             probes = {"f64" if not f32 else "f32": extras.get("probes")}
             if "config5_f32" in extras:
@@ -746,7 +780,7 @@ def main():
                 f.write(detail + "\n")
         if extras:
             print("BENCH_DETAIL " + detail, flush=True)
-        print(json.dumps(compact_line(line, len(detail))), flush=True)
+        print(json.dumps(compact_line(line, len(detail) if extras else None)), flush=True)
     if world > 1 or forced:
         dist.barrier()
         dist.destroy_process_group()

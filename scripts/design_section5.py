@@ -63,7 +63,7 @@ def main():
 
 `bench.py` (N=1): 1440×1080×75, 120 steps, fp64, global steric, θ/S resident (223.9 GB). Step = reference state (K0
 rho0 + volo; masso0 is masso(t=0) of the K1 launch) + K1 + stage-2 + area sum + host epilogue, K1 in the product's
-default arithmetic (fused, §3.1). **The output is two lines** since round 5: `BENCH_DETAIL {{…}}` (≈20 KB: every row
+default arithmetic (fused, §3.1). **The output of `--full` is two lines** since round 5: `BENCH_DETAIL {{…}}` (≈20 KB: every row
 with kernel name, notes, checks, the non-default float32 modes) and, LAST, the contract line (≈5 KB): the contract's
 keys, `roofline` -- with `per_kernel` {{key: [ms, fraction of 8 TB/s at algorithmic bytes, fraction of the matching
 probe, fraction of the live `v_fma_f64` probe]}} and `probes` {{dtype: {{mix: GB/s}}}} -- `cpu_baseline`, parity and a

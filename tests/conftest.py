@@ -117,7 +117,10 @@ def goldens():
 
 @pytest.fixture(scope="session")
 def wright_vectors():
-    return dict(np.load(os.path.join(GOLDEN, "wright_vectors.npz")))
+    # two files (the mixed-operand section on its own) so that each stays under 1 MiB
+    vectors = dict(np.load(os.path.join(GOLDEN, "wright_vectors.npz")))
+    vectors.update(np.load(os.path.join(GOLDEN, "wright_vectors_mixed.npz")))
+    return vectors
 
 
 @pytest.fixture(scope="session")

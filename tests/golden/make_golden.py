@@ -7,10 +7,10 @@ Run ONCE in the build container, where /root/reference exists:
 (-B: the process is root, a plain import would drop __pycache__ into the
 read-only reference tree.)
 
-Two files are written:
+Three files are written:
 
-* ``wright_vectors.npz`` -- inputs and the outputs of the REFERENCE'S OWN
-  ``src/momlevel/eos/wright.py`` (loaded standalone with importlib: the module
+* ``wright_vectors.npz`` and ``wright_vectors_mixed.npz`` (section (8)) --
+  inputs and the outputs of the REFERENCE'S OWN ``src/momlevel/eos/wright.py`` (loaded standalone with importlib: the module
   has no imports, the package itself is not importable here because xarray /
   xgcm / cftime are absent).  These pin the oracle's EOS restatement -- and,
   through it, the HIP kernels -- pointwise and bit for bit.
@@ -201,7 +201,11 @@ def main():
             ref.beta(18.0, 35.0, 200000.0),
         ]
     )
-    np.savez_compressed(os.path.join(HERE, "wright_vectors.npz"), **out)
+    # the mixed-operand section (8) in a file of its own: each file stays under 1 MiB
+    np.savez_compressed(os.path.join(HERE, "wright_vectors.npz"),
+                        **{k: v for k, v in out.items() if not k.startswith("mix_")})
+    np.savez_compressed(os.path.join(HERE, "wright_vectors_mixed.npz"),
+                        **{k: v for k, v in out.items() if k.startswith("mix_")})
 
     # ---- oracle-pinned steric cases on the reference's test dataset ----------
     from oracle import momlevel_numpy as o

@@ -274,3 +274,34 @@ def test_probe_fractions_follow_the_rows_mix():
     assert node["a"]["frac_of_matching_probe"] == 0.8
     assert node["b"]["c"]["frac_of_matching_probe"] == 0.5
     assert "frac_of_matching_probe" not in node["d"] and "frac_of_matching_probe" not in node["e"]
+
+
+def test_dump_outputs_writes_every_numeric_result_as_float64(tmp_path):
+    """--dump-outputs: what one timed step returned (parallel.finalize's dict), one float64 .npy
+    per array or scalar, the values unchanged."""
+    out = {"masso": np.array([1.5, 2.25, np.nan]), "eta": np.arange(3, dtype=np.float32),
+           "volo": np.float64(7.0), "area_sum": 3.0, "note": "not numeric"}
+    names = bench.dump_outputs(out, str(tmp_path / "outs"))
+    assert names == ["area_sum", "eta", "masso", "volo"]
+    for name in names:
+        got = np.load(tmp_path / "outs" / f"{name}.npy")
+        assert got.dtype == np.float64
+        assert np.array_equal(got, np.asarray(out[name], dtype=np.float64), equal_nan=True)
+
+
+def test_full_and_dump_outputs_options(monkeypatch):
+    """--full and --dump-outputs are off by default; --full leaves the extras' own options at their
+    defaults; --steps 0 (no timed step to report) is refused."""
+    import sys
+
+    import pytest
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and not a.no_extras and a.cpu_seconds > 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

@@ -153,3 +153,37 @@ def test_bench_force_collective_on_a_small_grid(tmp_path):
     assert fc["masso_bit_identical_to_plain_step"] and fc["eta_bit_identical_to_plain_step"]
     assert line["eta_t0_is_zero"] is True and line["roofline"]["launches_per_step"] == 5
     assert line["value"] > 0 and line["cpu_baseline"] is None  # (no CPU leg in this mode)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `python bench.py` (no --full) on a small grid, twice, as fresh processes: the contract
+    line alone (no BENCH_DETAIL, no CPU leg), --steps honoured, and --dump-outputs writing the last
+    timed step's results -- identical from run to run and equal to the line's own masso(t=0)."""
+    import json
+
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    lines = []
+    for k in range(2):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "9,48,128",
+                            "--nt", "13", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / f"out{k}")], env=env, capture_output=True, text=True,
+                           timeout=280)
+        assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
+        assert not any(t.startswith("BENCH_DETAIL") for t in p.stdout.splitlines())
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        assert "detail" not in lines[-1]
+    for line in lines:
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["unit"] == "Mcells/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["cpu_baseline"] is None and line["eta_t0_is_zero"] is True
+    names = sorted(os.listdir(tmp_path / "out0"))
+    assert names == sorted(os.listdir(tmp_path / "out1"))
+    assert {"masso.npy", "eta.npy", "expansion_coeff.npy", "masso0.npy"} <= set(names)
+    for name in names:
+        a, b = np.load(tmp_path / "out0" / name), np.load(tmp_path / "out1" / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), name
+    masso = np.load(tmp_path / "out0" / "masso.npy")
+    assert masso.shape == (13,) and masso[0] == np.load(tmp_path / "out0" / "masso0.npy")
+    assert np.load(tmp_path / "out0" / "eta.npy")[0] == 0.0
