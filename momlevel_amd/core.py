@@ -454,29 +454,52 @@ def steric_global_masso(T, S, vol0, p, eos="wright", f32_mode="faithful", events
     hint, time steps per block (multiple of 8; 0 = library default); never changes a result.
     ``p`` may be time dependent, (nt,nz,ny,nx)-broadcastable (a DataArray ``patm``).
     """
+    return _steric_global("mlx_steric_global", T, S, None, vol0, p, eos, f32_mode, events,
+                          skip_dry, arith, t_chunk)
+
+
+def _held_pair(entry, T, S, T0, S0):
+    """The reference fields (T0, S0) of an all-variants launch ``entry`` over the validated
+    fields T, S: on their device, in their dtypes, contiguous."""
+    if T.dim() != 4 or S.dim() != 4:
+        raise ValueError(f"{entry[4:]} streams both fields: thetao and so must be 4-D")
+    shape3 = tuple(T.shape[1:])
+    T0 = T0.to(device=T.device, dtype=T.dtype).contiguous()
+    S0 = S0.to(device=T.device, dtype=S.dtype).contiguous()
+    if tuple(T0.shape) != shape3 or tuple(S0.shape) != shape3:
+        raise ValueError(f"T0 and S0 must be {shape3}")
+    return T0, S0
+
+
+def _steric_global(entry, T, S, held, vol0, p, eos, f32_mode, events, skip_dry, arith, t_chunk):
+    """The frame of both K1 entry points (one body, as steric_global_impl on the C side):
+    ``held`` None -> mlx_steric_global, (nt,) out; (T0, S0) -> mlx_steric_global_decomp, (4, nt)."""
     require_device()
     T, S, nt, nz, ny, nx, sT, sS, dt, _ = _pair(T, S, f32_mode)
     flags = _launch_flags(skip_dry, arith, t_chunk, "k1", dt)
-    vol0 = _f64(vol0, T.device)
+    dev = T.device
+    if held is not None:
+        held = _held_pair(entry, T, S, *held)
+    vol0 = _f64(vol0, dev)
     if tuple(vol0.shape) != (nz, ny, nx):
         raise ValueError(f"vol0 has shape {tuple(vol0.shape)}, expected {(nz, ny, nx)}")
-    pt, p_mode = _pressure(p, nt, nz, ny, nx, T.device, allow4d=True)
+    pt, p_mode = _pressure(p, nt, nz, ny, nx, dev, allow4d=True)
     lib = _lib.load()
-    nbytes = lib.mlx_steric_global_workspace_bytes(nt, nz, ny * nx)
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=T.device)
-    out = torch.empty(nt, dtype=torch.float64, device=T.device)
-    with _on(T.device):
-        stream = torch.cuda.current_stream(T.device)
+    nbytes = getattr(lib, entry + "_workspace_bytes")(nt, nz, ny * nx)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(nt if held is None else (4, nt), dtype=torch.float64, device=dev)
+    with _on(dev):
+        stream = torch.cuda.current_stream(dev)
         if events is not None:
             events[0].record(stream)
-        rc = lib.mlx_steric_global(
-            _ptr(T), _ptr(S), dt, _ptr(vol0), _ptr(pt), p_mode, EOS_IDS[eos.lower()],
-            nt, nz, ny * nx, sT, sS, flags,
-            _ptr(out), _ptr(ws), nbytes, stream.cuda_stream,
+        rc = getattr(lib, entry)(
+            _ptr(T), _ptr(S), *map(_ptr, held or ()), dt, _ptr(vol0), _ptr(pt), p_mode,
+            EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, flags, _ptr(out), _ptr(ws), nbytes,
+            stream.cuda_stream,
         )
         if events is not None:
             events[1].record(stream)
-    _lib.check(rc, "mlx_steric_global")
+    _lib.check(rc, entry)
     return out
 
 
@@ -489,37 +512,8 @@ def steric_global_decomp(T, S, T0, S0, vol0, p, eos="wright", f32_mode="faithful
     masso of steric / thermosteric (S held at S0) / halosteric (theta held at T0), and
     sum(theta*vol0) (the heat-content integrand; an extension, not in momlevel).  Rows 0-2 are
     bit-identical to three steric_global_masso calls."""
-    require_device()
-    T, S, nt, nz, ny, nx, sT, sS, dt, _ = _pair(T, S, f32_mode)
-    flags = _launch_flags(skip_dry, arith, t_chunk, "k1", dt)
-    if T.dim() != 4 or S.dim() != 4:
-        raise ValueError("steric_global_decomp streams both fields: thetao and so must be 4-D")
-    dev = T.device
-    T0 = T0.to(device=dev, dtype=T.dtype).contiguous()
-    S0 = S0.to(device=dev, dtype=S.dtype).contiguous()
-    if tuple(T0.shape) != (nz, ny, nx) or tuple(S0.shape) != (nz, ny, nx):
-        raise ValueError(f"T0 and S0 must be {(nz, ny, nx)}")
-    vol0 = _f64(vol0, dev)
-    if tuple(vol0.shape) != (nz, ny, nx):
-        raise ValueError(f"vol0 has shape {tuple(vol0.shape)}, expected {(nz, ny, nx)}")
-    pt, p_mode = _pressure(p, nt, nz, ny, nx, dev, allow4d=True)
-    lib = _lib.load()
-    nbytes = lib.mlx_steric_global_decomp_workspace_bytes(nt, nz, ny * nx)
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    out = torch.empty((4, nt), dtype=torch.float64, device=dev)
-    with _on(dev):
-        stream = torch.cuda.current_stream(dev)
-        if events is not None:
-            events[0].record(stream)
-        rc = lib.mlx_steric_global_decomp(
-            _ptr(T), _ptr(S), _ptr(T0), _ptr(S0), dt, _ptr(vol0), _ptr(pt), p_mode,
-            EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, flags, _ptr(out), _ptr(ws), nbytes,
-            stream.cuda_stream,
-        )
-        if events is not None:
-            events[1].record(stream)
-    _lib.check(rc, "mlx_steric_global_decomp")
-    return out
+    return _steric_global("mlx_steric_global_decomp", T, S, (T0, S0), vol0, p, eos, f32_mode,
+                          events, skip_dry, arith, t_chunk)
 
 
 def stream_probe(a, b, out=None):
@@ -580,15 +574,17 @@ def fold_mask(rho0, vol0):
     return out
 
 
-def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=None,
-                 deptho=None, eos="wright", f32_mode="faithful", want_delta_rho=True,
-                 delta_rho_out=None, eta_out=None, skip_dry=None, arith=None):
-    """K2: (delta_rho (nt,nz,ny,nx) or None, eta (nt,ny,nx)).  ``skip_dry``, ``arith``: see
-    steric_global_masso.  ``p`` may be time dependent (4-D)."""
+def _steric_local(entry, T, S, held, rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i, deptho, eos,
+                  f32_mode, skip_dry, arith):
+    """The operands both K2 entry points take (``held``: None, or the (T0, S0) of the all-variants
+    launch), validated and on the device -> (device, (nt, nz, ny, nx), launch): ``launch(*outputs)``
+    enqueues ``entry`` with the output arguments that follow the common ones."""
     require_device()
     T, S, nt, nz, ny, nx, sT, sS, dt, _ = _pair(T, S, f32_mode)
     flags = _launch_flags(skip_dry, arith, 0, "k2", dt)
     dev = T.device
+    if held is not None:
+        held = _held_pair(entry, T, S, *held)
     rho0m = _f64(rho0m, dev)
     vol0_surface = _f64(vol0_surface, dev)
     if tuple(rho0m.shape) != (nz, ny, nx) or tuple(vol0_surface.shape) != (ny, nx):
@@ -603,6 +599,27 @@ def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=Non
         deptho = _f64(deptho, dev)
         if z_i.numel() != nz + 1 or tuple(deptho.shape) != (ny, nx):
             raise ValueError("z_i must have nz+1 entries and deptho be (ny,nx)")
+
+    def launch(*outputs):
+        with _on(dev):
+            rc = getattr(_lib.load(), entry)(
+                _ptr(T), _ptr(S), *map(_ptr, held or ()), dt, _ptr(rho0m), _ptr(vol0_surface),
+                _ptr(dz), _ptr(z_i), _ptr(deptho), _ptr(pt), p_mode, EOS_IDS[eos.lower()],
+                float(neg_inv_rhozero), nt, nz, ny * nx, sT, sS, flags, *outputs, _stream(dev),
+            )
+        _lib.check(rc, entry)
+
+    return dev, (nt, nz, ny, nx), launch
+
+
+def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=None,
+                 deptho=None, eos="wright", f32_mode="faithful", want_delta_rho=True,
+                 delta_rho_out=None, eta_out=None, skip_dry=None, arith=None):
+    """K2: (delta_rho (nt,nz,ny,nx) or None, eta (nt,ny,nx)).  ``skip_dry``, ``arith``: see
+    steric_global_masso.  ``p`` may be time dependent (4-D)."""
+    dev, (nt, nz, ny, nx), launch = _steric_local(
+        "mlx_steric_local", T, S, None, rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i, deptho,
+        eos, f32_mode, skip_dry, arith)
     drho = None
     if want_delta_rho:
         drho = delta_rho_out
@@ -611,14 +628,7 @@ def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=Non
     eta = eta_out if eta_out is not None else torch.empty(
         (nt, ny, nx), dtype=torch.float64, device=dev
     )
-    with _on(dev):
-        rc = _lib.load().mlx_steric_local(
-            _ptr(T), _ptr(S), dt, _ptr(rho0m), _ptr(vol0_surface), _ptr(dz), _ptr(z_i),
-            _ptr(deptho), _ptr(pt), p_mode, EOS_IDS[eos.lower()], float(neg_inv_rhozero),
-            nt, nz, ny * nx, sT, sS, flags,
-            _ptr(drho), _ptr(eta), _stream(dev),
-        )
-    _lib.check(rc, "mlx_steric_local")
+    launch(_ptr(drho), _ptr(eta))
     return drho, eta
 
 
@@ -632,30 +642,9 @@ def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, d
     eta (3,nt,ny,nx)), variant order LOCAL_DECOMP_ROWS; each field bit-identical to its
     steric_local call.  ``delta_rho_out`` / ``eta_out``: optional (3, nt, ...) float64 device
     tensors (or views whose variant axis has any stride, e.g. ``full[:, t0:t1]``)."""
-    require_device()
-    T, S, nt, nz, ny, nx, sT, sS, dt, _ = _pair(T, S, f32_mode)
-    flags = _launch_flags(skip_dry, arith, 0, "k2", dt)
-    if T.dim() != 4 or S.dim() != 4:
-        raise ValueError("steric_local_decomp streams both fields: thetao and so must be 4-D")
-    dev = T.device
-    T0 = T0.to(device=dev, dtype=T.dtype).contiguous()
-    S0 = S0.to(device=dev, dtype=S.dtype).contiguous()
-    if tuple(T0.shape) != (nz, ny, nx) or tuple(S0.shape) != (nz, ny, nx):
-        raise ValueError(f"T0 and S0 must be {(nz, ny, nx)}")
-    rho0m = _f64(rho0m, dev)
-    vol0_surface = _f64(vol0_surface, dev)
-    if tuple(rho0m.shape) != (nz, ny, nx) or tuple(vol0_surface.shape) != (ny, nx):
-        raise ValueError("rho0m must be (nz,ny,nx) and vol0_surface (ny,nx)")
-    pt, p_mode = _pressure(p, nt, nz, ny, nx, dev, allow4d=True)
-    if dz is not None:
-        dz = _f64(dz, dev)
-        if tuple(dz.shape) != (nz, ny, nx):
-            raise ValueError("dz must be (nz,ny,nx)")
-    else:
-        z_i = _f64(z_i, dev)
-        deptho = _f64(deptho, dev)
-        if z_i.numel() != nz + 1 or tuple(deptho.shape) != (ny, nx):
-            raise ValueError("z_i must have nz+1 entries and deptho be (ny,nx)")
+    dev, (nt, nz, ny, nx), launch = _steric_local(
+        "mlx_steric_local_decomp", T, S, (T0, S0), rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i,
+        deptho, eos, f32_mode, skip_dry, arith)
 
     def variant_major(x, shape):
         """(3, nt, ...) float64 device tensor whose per-variant fields are contiguous"""
@@ -673,15 +662,7 @@ def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, d
     eta = eta_out if eta_out is not None else torch.empty((3, nt, ny, nx), dtype=torch.float64,
                                                            device=dev)
     variant_major(eta, (3, nt, ny, nx))
-    with _on(dev):
-        rc = _lib.load().mlx_steric_local_decomp(
-            _ptr(T), _ptr(S), _ptr(T0), _ptr(S0), dt, _ptr(rho0m), _ptr(vol0_surface), _ptr(dz),
-            _ptr(z_i), _ptr(deptho), _ptr(pt), p_mode, EOS_IDS[eos.lower()],
-            float(neg_inv_rhozero), nt, nz, ny * nx, sT, sS, flags,
-            _ptr(drho), drho.stride(0) if drho is not None else 0, _ptr(eta), eta.stride(0),
-            _stream(dev),
-        )
-    _lib.check(rc, "mlx_steric_local_decomp")
+    launch(_ptr(drho), drho.stride(0) if drho is not None else 0, _ptr(eta), eta.stride(0))
     return drho, eta
 
 

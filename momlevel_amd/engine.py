@@ -10,6 +10,7 @@ state stays resident on the device.  Every byte moves through hostio.py: staging
 result buffers of our own, never a GPU mapping of the caller's memory.
 """
 
+import contextlib
 import warnings
 
 import numpy as np
@@ -280,22 +281,31 @@ def global_masso(T, S, vol0, pres, eos="wright", f32_mode="faithful", steps=None
     Device-resident fields are processed by ONE K1 launch over all time steps; host
     fields in time chunks.  ``events``: see core.steric_global_masso (single launch only).
     """
+    nt, vol0, chunks = _global_chunks(T, S, vol0, pres, steps)
+    out = None
+    for t0, t1, Tc, Sc, pc in chunks:
+        whole = t1 - t0 == nt  # the record in ONE launch: its tensor is the result, nothing copied
+        masso = core.steric_global_masso(Tc, Sc, vol0, pc, eos=eos, f32_mode=f32_mode,
+                                         events=events if whole else None, skip_dry=skip_dry)
+        if whole:
+            return masso
+        if out is None:
+            out = torch.empty(nt, dtype=torch.float64, device=vol0.device)
+        out[t0:t1] = masso
+    return out
+
+
+def _global_chunks(T, S, vol0, pres, steps):
+    """Set-up and time loop of the global passes -> (nt, vol0 on the device, iterator over
+    ``(t0, t1, Tc, Sc, pressure of the chunk)``)."""
     dev = device_of(T, S, vol0)
     vol0 = to_device(vol0, dev, torch.float64)
     if not time_dependent(pres):
         pres = to_device(pres, dev, torch.float64)
     chunks = TimeChunks(T, S, dev, steps=steps,
                         extra_bytes_per_step=_pressure_bytes_per_step(pres))
-    if chunks.steps >= chunks.nt:
-        for t0, t1, Tc, Sc in chunks:
-            return core.steric_global_masso(Tc, Sc, vol0, pressure_chunk(pres, t0, t1, dev),
-                                            eos=eos, f32_mode=f32_mode, events=events,
-                                            skip_dry=skip_dry)
-    out = torch.empty(chunks.nt, dtype=torch.float64, device=dev)
-    for t0, t1, Tc, Sc in chunks:
-        out[t0:t1] = core.steric_global_masso(Tc, Sc, vol0, pressure_chunk(pres, t0, t1, dev),
-                                              eos=eos, f32_mode=f32_mode, skip_dry=skip_dry)
-    return out
+    return chunks.nt, vol0, ((t0, t1, Tc, Sc, pressure_chunk(pres, t0, t1, dev))
+                             for t0, t1, Tc, Sc in chunks)
 
 
 def global_finalize(masso, volo, rhoga, area_sum):
@@ -327,66 +337,6 @@ def _host_output(shape):
     numpy array when small, page-locked memory when the caller opted in; see
     hostio.result_array."""
     return hostio.result_array(shape, np.float64)
-
-
-def local_steric(T, S, rho0, vol0, pres, rhozero, z_i=None, deptho=None, dz=None,
-                 eos="wright", f32_mode="faithful", want_delta_rho=True, out_host=None,
-                 steps=None):
-    """delta_rho (nt,nz,ny,nx) [optional] and eta (nt,ny,nx).
-
-    ``out_host=True`` returns numpy arrays filled chunk by chunk (for host inputs
-    larger than HBM); otherwise device tensors.
-    """
-    dev = device_of(T, S, rho0, vol0)
-    vol0 = to_device(vol0, dev, torch.float64)
-    rho0 = to_device(rho0, dev, torch.float64)
-    if not time_dependent(pres):
-        pres = to_device(pres, dev, torch.float64)
-    rho0m = core.fold_mask(rho0, vol0)
-    surface = vol0[0].contiguous()
-    if dz is not None:
-        dz = to_device(dz, dev, torch.float64)
-    else:
-        z_i = to_device(z_i, dev, torch.float64)
-        deptho = to_device(deptho, dev, torch.float64)
-    neg_inv = -1.0 / float(rhozero)
-    nz, ny, nx = tuple(vol0.shape)
-    n3 = nz * ny * nx
-    if out_host is None:
-        out_host = not (_is_device(T) or _is_device(S))
-    extra = (n3 * 8 if (want_delta_rho and out_host) else 0) + _pressure_bytes_per_step(pres)
-    chunks = TimeChunks(T, S, dev, steps=steps, extra_bytes_per_step=extra, ramp=out_host)
-    nt = chunks.nt
-    if out_host:
-        eta = _host_output((nt, ny, nx))
-        drho = _host_output((nt, nz, ny, nx)) if want_delta_rho else None
-    else:
-        eta = torch.empty((nt, ny, nx), dtype=torch.float64, device=dev)
-        drho = (
-            torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=dev)
-            if want_delta_rho else None
-        )
-    # results go back on a stream and a worker thread of their own (hostio.Downloader): the D2H of
-    # chunk k overlaps the H2D of chunk k+1 (PCIe is full duplex, the copies use different DMA
-    # engines) and this loop goes straight on to chunk k+1's kernels
-    if not out_host:
-        for t0, t1, Tc, Sc in chunks:
-            core.steric_local(Tc, Sc, rho0m, surface, pressure_chunk(pres, t0, t1, dev), neg_inv,
-                              dz=dz, z_i=z_i, deptho=deptho, eos=eos, f32_mode=f32_mode,
-                              want_delta_rho=want_delta_rho,
-                              delta_rho_out=drho[t0:t1] if want_delta_rho else None,
-                              eta_out=eta[t0:t1])
-        return drho, eta
-    with hostio.Downloader(dev) as results:
-        for t0, t1, Tc, Sc in chunks:
-            pc = pressure_chunk(pres, t0, t1, dev)
-            d, e = core.steric_local(Tc, Sc, rho0m, surface, pc, neg_inv, dz=dz, z_i=z_i,
-                                     deptho=deptho, eos=eos, f32_mode=f32_mode,
-                                     want_delta_rho=want_delta_rho)
-            # straight into the caller-visible arrays (one D2H pass, no intermediate array)
-            results.submit([(eta[t0:t1], e)] + ([(drho[t0:t1], d)] if want_delta_rho else []))
-    # (the host arrays are complete: the with-block waits for the last piece)
-    return drho, eta
 
 
 # ---------------------------------------------------------------------------------------
@@ -425,22 +375,17 @@ def global_masso_variants(T, S, T0, S0, vol0, pres, variants, eos="wright", f32_
     by its own launch.  Either way every row is bit-identical to the single-variant call, and
     theta/S chunks of host inputs are uploaded once."""
     dev = device_of(T, S, vol0)
-    vol0 = to_device(vol0, dev, torch.float64)
-    if not time_dependent(pres):
-        pres = to_device(pres, dev, torch.float64)
     T0 = to_device(T0, dev, _stream_dtype(T0))
     S0 = to_device(S0, dev, _stream_dtype(S0))
     same = _reference_matches(T, S, T0, S0)
     one_pass = (len(variants) >= 2 and same) or with_heat
     heat_only = one_pass and not same  # the heat row does not depend on the reference fields
     Ts, Ss = (T, S) if one_pass else _streamed_pair(variants, T, S, T0, S0)
-    chunks = TimeChunks(Ts, Ss, dev, steps=steps,
-                        extra_bytes_per_step=_pressure_bytes_per_step(pres))
+    _, vol0, chunks = _global_chunks(Ts, Ss, vol0, pres, steps)
     nt = T.shape[0]
     names = list(variants) + (["heat"] if with_heat else [])
     out = {v: torch.empty(nt, dtype=torch.float64, device=dev) for v in names}
-    for t0, t1, Tc, Sc in chunks:
-        pc = pressure_chunk(pres, t0, t1, dev)
+    for t0, t1, Tc, Sc, pc in chunks:
         if one_pass:
             rows = core.steric_global_decomp(Tc, Sc, T0.to(Tc.dtype), S0.to(Sc.dtype), vol0, pc,
                                              eos=eos, f32_mode=f32_mode, skip_dry=skip_dry)
@@ -455,40 +400,48 @@ def global_masso_variants(T, S, T0, S0, vol0, pres, variants, eos="wright", f32_
     return out
 
 
+def _local_operands(T, S, rho0, vol0, pres, rhozero, z_i, deptho, dz, out_host):
+    """The time-invariant operands of the local pass, on the device of (T, S, rho0, vol0) ->
+    (device, pressure, out_host, (rho0m, surface volume, -1/rhozero), the dz | z_i + deptho
+    keywords of core.steric_local*).  ``out_host`` None: host results for host fields."""
+    dev = device_of(T, S, rho0, vol0)
+    vol0 = to_device(vol0, dev, torch.float64)
+    rho0 = to_device(rho0, dev, torch.float64)
+    if not time_dependent(pres):
+        pres = to_device(pres, dev, torch.float64)
+    if dz is not None:
+        depth = dict(dz=to_device(dz, dev, torch.float64))
+    else:
+        depth = dict(z_i=to_device(z_i, dev, torch.float64),
+                     deptho=to_device(deptho, dev, torch.float64))
+    if out_host is None:
+        out_host = not (_is_device(T) or _is_device(S))
+    fixed = (core.fold_mask(rho0, vol0), vol0[0].contiguous(), -1.0 / float(rhozero))
+    return dev, pres, out_host, fixed, depth
+
+
 def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i=None,
                           deptho=None, dz=None, eos="wright", f32_mode="faithful",
                           want_delta_rho=True, out_host=None, steps=None, annual_weights=None,
                           reference_is_step0=False):
     """{variant: (delta_rho, eta)}; theta/S chunks are uploaded once and reused.
 
+    ``out_host=True`` returns numpy arrays filled chunk by chunk (for host inputs larger than
+    HBM); otherwise device tensors (None: host arrays for host fields).
     ``annual_weights`` (nt,), nt a multiple of 12, whole years back to back: the days-in-month
     weighted annual means (util.annual_average) are taken ON THE DEVICE, chunk by chunk, so only
     1/12 of delta_rho / eta is ever stored or copied back; the outputs are (nt/12, ...).
     ``reference_is_step0``: (T0, S0) ARE time level 0 of (T, S) -- a reference state steric() made
     itself: the first chunk of a host record is then that step, taken from the device.
     """
-    dev = device_of(T, S, rho0, vol0)
-    vol0 = to_device(vol0, dev, torch.float64)
-    rho0 = to_device(rho0, dev, torch.float64)
-    if not time_dependent(pres):
-        pres = to_device(pres, dev, torch.float64)
+    dev, pres, out_host, (rho0m, surface, neg_inv), depth = _local_operands(
+        T, S, rho0, vol0, pres, rhozero, z_i, deptho, dz, out_host)
     T0 = to_device(T0, dev, _stream_dtype(T0))
     S0 = to_device(S0, dev, _stream_dtype(S0))
-    rho0m = core.fold_mask(rho0, vol0)
-    surface = vol0[0].contiguous()
-    if dz is not None:
-        dz = to_device(dz, dev, torch.float64)
-    else:
-        z_i = to_device(z_i, dev, torch.float64)
-        deptho = to_device(deptho, dev, torch.float64)
-    neg_inv = -1.0 / float(rhozero)
-    nz, ny, nx = tuple(vol0.shape)
+    nz, ny, nx = tuple(rho0m.shape)
     nt = T.shape[0]
-    if out_host is None:
-        out_host = not (_is_device(T) or _is_device(S))
-    n_out = len(variants)
     annual = annual_weights is not None
-    extra = n_out * nz * ny * nx * 8 if (want_delta_rho and (out_host or annual)) else 0
+    extra = len(variants) * nz * ny * nx * 8 if (want_delta_rho and (out_host or annual)) else 0
     extra += _pressure_bytes_per_step(pres)
     Ts, Ss = _streamed_pair(variants, T, S, T0, S0)
     if annual:
@@ -527,11 +480,11 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
     else:
         eta = {v: alloc((nt_out, ny, nx)) for v in variants}
         drho = {v: (alloc((nt_out, nz, ny, nx)) if want_delta_rho else None) for v in variants}
-    kw = dict(dz=dz, z_i=z_i, deptho=deptho, eos=eos, f32_mode=f32_mode,
-              want_delta_rho=want_delta_rho)
-    import contextlib
+    in_place = not out_host and not annual  # per-variant launches write the device outputs too
+    kw = dict(depth, eos=eos, f32_mode=f32_mode, want_delta_rho=want_delta_rho)
 
-    # host results leave on a stream and a worker thread of their own (hostio.Downloader)
+    # host results leave on a stream and a worker thread of their own (hostio.Downloader): the D2H
+    # of chunk k overlaps the H2D of chunk k+1 and this loop goes straight on to chunk k+1's kernels
     with (hostio.Downloader(dev) if out_host else contextlib.nullcontext()) as results:
         for t0, t1, Tc, Sc in chunks:
             o0, o1 = (t0 // 12, t1 // 12) if annual else (t0, t1)
@@ -544,32 +497,29 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
                 continue
             if one_pass:
                 d3, e3 = core.steric_local_decomp(Tc, Sc, T0, S0, rho0m, surface, pc, neg_inv, **kw)
-                chunk_fields = {v: (d3[i] if want_delta_rho else None, e3[i])
-                                for i, v in enumerate(rows)}
             going_out = []
             for v in variants:
-                Tv, Sv = _variant_operands(v, Tc, Sc, T0, S0)
-                if annual:  # K2 on the chunk, then the fused annual-mean epilogue on the device
-                    d, e = (chunk_fields[v] if one_pass else
-                            core.steric_local(Tv, Sv, rho0m, surface, pc, neg_inv, **kw))
+                # produce (d, e) of the chunk: a slice of the one pass, or the variant's own launch
+                if one_pass:
+                    d, e = (d3[rows.index(v)] if want_delta_rho else None), e3[rows.index(v)]
+                else:
+                    Tv, Sv = _variant_operands(v, Tc, Sc, T0, S0)
+                    into = dict(delta_rho_out=drho[v][t0:t1] if want_delta_rho else None,
+                                eta_out=eta[v][t0:t1]) if in_place else {}
+                    d, e = core.steric_local(Tv, Sv, rho0m, surface, pc, neg_inv, **into, **kw)
+                # reduce: the fused annual-mean epilogue, on the device
+                if annual:
                     e = core.group_weighted_mean(e, w_dev[t0:t1], 12,
                                                  out=None if out_host else eta[v][o0:o1])
                     if want_delta_rho:
                         d = core.group_weighted_mean(d, w_dev[t0:t1], 12,
                                                      out=None if out_host else drho[v][o0:o1])
-                    if not out_host:
-                        continue
+                # deliver: straight into the caller-visible arrays (one D2H pass); device results
+                # have been written where they belong
                 if out_host:
-                    if not annual:
-                        d, e = (chunk_fields[v] if one_pass else
-                                core.steric_local(Tv, Sv, rho0m, surface, pc, neg_inv, **kw))
                     going_out.append((eta[v][o0:o1], e))
                     if want_delta_rho:
                         going_out.append((drho[v][o0:o1], d))
-                else:
-                    core.steric_local(Tv, Sv, rho0m, surface, pc, neg_inv,
-                                      delta_rho_out=drho[v][t0:t1] if want_delta_rho else None,
-                                      eta_out=eta[v][t0:t1], **kw)
             if going_out:
                 results.submit(going_out)
     return {v: (drho[v], eta[v]) for v in variants}

@@ -32,7 +32,7 @@ allreduce`` selects the library's own ``all_reduce(SUM)`` instead (same bytes on
 up to the factor N; results within 1 ulp per element of the ordered sum, no exact-zero guarantee).
 
 The local variants need no collective at all (columns are independent): each
-rank simply runs ``engine.local_steric`` on its tile.
+rank simply runs ``engine.local_steric_variants`` on its tile.
 """
 
 import os
@@ -462,17 +462,12 @@ def steric_local_tile(T, S, vol0, pres, z_i, deptho, rhozero=1035.0, variant="st
     """
     from . import core
 
-    if variant == "thermosteric":
-        Tv, Sv = T, S[0]
-    elif variant == "halosteric":
-        Tv, Sv = T[0], S
-    elif variant == "steric":
-        Tv, Sv = T, S
-    else:
+    if variant not in _VARIANTS:
         raise ValueError(f"Unknown variant '{variant}' passed to `steric`")
     rho0 = core.eos_map(T[0], S[0], pres, eos=eos, f32_mode=f32_mode)
-    return engine.local_steric(Tv, Sv, rho0, vol0, pres, rhozero, z_i=z_i, deptho=deptho, eos=eos,
-                               f32_mode=f32_mode, want_delta_rho=want_delta_rho, out_host=False)
+    return engine.local_steric_variants(
+        T, S, T[0], S[0], rho0, vol0, pres, rhozero, (variant,), z_i=z_i, deptho=deptho, eos=eos,
+        f32_mode=f32_mode, want_delta_rho=want_delta_rho, out_host=False)[variant]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ Inputs: labelled datasets backed by numpy (streamed to HBM in time chunks) or by
 tensors (processed in place); xarray Datasets when xarray is installed (adapters.py).
 """
 
+import contextlib
 import os
 
 import numpy as np
@@ -207,18 +208,30 @@ def globalise_reference(reference, exchange):
     set_reference_masso(reference, vec[1])
 
 
-def _steric_many(*args, **kwargs):
-    """_steric_body with what the reference state left in flight completed before anything is
-    returned or raised (reference._setup sends rho0 to the host asynchronously)."""
+@contextlib.contextmanager
+def _completing_pending():
+    """-> the ``twins`` dict of one _steric_body; the download it left in ``twins["pending"]``
+    (reference._setup sends rho0 to the host asynchronously) is completed when the block ends:
+    finished when the block succeeded -- whatever exception the CALLER may be handling around it --
+    and, when the block itself raised, drained with that error kept."""
     twins = {}
     try:
-        return _steric_body(twins, *args, **kwargs)
-    finally:
+        yield twins
+    except BaseException as exc:
         pending = twins.pop("pending", None)
         if pending is not None:
-            import sys
+            pending.__exit__(type(exc), exc, exc.__traceback__)
+        raise
+    pending = twins.pop("pending", None)
+    if pending is not None:
+        pending.__exit__(None, None, None)  # finish(), then the worker is shut down
 
-            pending.__exit__(*sys.exc_info())  # (finish(); on an error: drain, keep the error)
+
+def _steric_many(*args, **kwargs):
+    """_steric_body with what the reference state left in flight completed before anything is
+    returned or raised."""
+    with _completing_pending() as twins:
+        return _steric_body(twins, *args, **kwargs)
 
 
 def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rhozero, patm,

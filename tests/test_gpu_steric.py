@@ -1326,3 +1326,29 @@ def test_a_float32_depth_coordinate_is_followed_or_refused_never_widened(domain,
     assert_bit_equal(rho.values, v["f32z_density"], "calc_rho, float32 fields and pressure")
     rho = derived.calc_rho(DataArray(v["blk_T"], dims, coords), DataArray(v["blk_S"], dims, coords), pres)
     assert_bit_equal(rho.values, v["f32z_density_f64fields"], "calc_rho, float64 fields, float32 pressure")
+
+
+def test_steric_inside_an_except_block_completes_the_reference_density(monkeypatch):
+    """a host-input steric() that SUCCEEDS while its caller is handling an
+    exception of its own finishes the deferred rho0 download like any other call (it used to be
+    treated as failed: jobs cancelled, errors swallowed) -- reference["rho"] bit for bit the plain
+    call's, on the deferred path (the threshold is made small enough for the test grid)."""
+    from momlevel_amd import hostio
+
+    monkeypatch.setattr(hostio, "SMALL_BYTES", 1 << 10)
+    d = _masked_dataset(nt=5, nz=9, ny=28, nx=40)
+    deferred = []
+    real = hostio.Downloader.finish
+    monkeypatch.setattr(hostio.Downloader, "finish", lambda self: deferred.append(1) or real(self))
+    base, bref = steric(d, domain="global")  # (global: the ONLY Downloader is the pending rho0's)
+    assert len(deferred) == 1, "the test grid must take the deferred rho0 path"
+    try:
+        raise KeyError("the caller's own, handled")
+    except KeyError:
+        res, ref = steric(d, domain="global")
+        lres, lref = steric(d)
+    assert len(deferred) >= 3
+    assert_bit_equal(ref["rho"].values, bref["rho"].values)
+    assert_bit_equal(lref["rho"].values, bref["rho"].values)
+    assert not np.isnan(ref["rho"].values).all()
+    assert_bit_equal(res["steric"].values, base["steric"].values)

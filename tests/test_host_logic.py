@@ -755,3 +755,52 @@ def test_small_integer_masked_sources_in_memory_follow_xarray_lazy_ones_are_docu
     assert mask is None and plain.dtype == np.float64 and np.isnan(plain[0, 0, 0]) and plain[0, 0, 1] == 1.0
     assert "int16" in check_field_dtype.__doc__ and "parity unpinned" in check_field_dtype.__doc__
     del lazy
+
+
+class _PendingStub:
+    """what steric._completing_pending sees of a hostio.Downloader: records how it was completed"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __exit__(self, exc_type, exc, tb):
+        self.calls.append("finish" if exc_type is None else ("drain", exc_type, exc))
+        return False
+
+
+def test_pending_download_is_finished_when_steric_succeeds_inside_an_except_block():
+    """steric() called from a caller's ``except`` block used to read the caller's
+    HANDLED exception from sys.exc_info() and take the Downloader's failure branch (jobs cancelled,
+    flush errors swallowed): reference["rho"] could come back unfilled without an error.  The
+    completion follows the body's own outcome only."""
+    from momlevel_amd.steric import _completing_pending
+
+    stub = _PendingStub()
+    try:
+        raise KeyError("the caller's own, handled")
+    except KeyError:
+        with _completing_pending() as twins:
+            twins["pending"] = stub
+    assert stub.calls == ["finish"] and "pending" not in twins
+    with _completing_pending() as twins:  # (nothing in flight: nothing to complete)
+        pass
+    assert twins == {}
+
+
+def test_pending_download_is_drained_and_the_bodys_error_kept():
+    from momlevel_amd.steric import _completing_pending
+
+    stub = _PendingStub()
+    boom = OSError("the body's error")
+    with pytest.raises(OSError) as caught:
+        with _completing_pending() as twins:
+            twins["pending"] = stub
+            raise boom
+    assert caught.value is boom
+    assert stub.calls == [("drain", OSError, boom)]
+    stub = _PendingStub()
+    with pytest.raises(KeyboardInterrupt):  # (not an Exception: still drained, still re-raised)
+        with _completing_pending() as twins:
+            twins["pending"] = stub
+            raise KeyboardInterrupt
+    assert [c[0] for c in stub.calls] == ["drain"]
