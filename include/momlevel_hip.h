@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MLX_ABI_VERSION 8 /* 2: mlx_eos_map takes flags; mlx_steric_global_decomp, mlx_steric_local_decomp,
+#define MLX_ABI_VERSION 9 /* 2: mlx_eos_map takes flags; mlx_steric_global_decomp, mlx_steric_local_decomp,
                              mlx_stream_probe;
                              MLX_FLAG_FMA, MLX_FLAG_TCHUNK; MLX_P_FULL4D in K1/K2
                              3: mlx_build_kind; a NULL p (linear EOS) requires p_mode MLX_P_SCALAR
@@ -47,7 +47,8 @@ extern "C" {
                              6: mlx_host_copy; mlx_stratification, mlx_adjust_negative_n2,
                                 mlx_wave_speed_where_time0
                              7: mlx_host_copy_masked
-                             8: MLX_FUNC_DENSITY_REF in mlx_eos_map_promote */
+                             8: MLX_FUNC_DENSITY_REF in mlx_eos_map_promote
+                             9: MLX_FLAG_DRHO_F32 in mlx_steric_local / mlx_steric_local_decomp */
 
 /* argument-error codes (negative) */
 #define MLX_E_NULL     (-1) /* a required pointer is NULL                      */
@@ -115,6 +116,11 @@ extern "C" {
                                sum off the fp64-VALU bound.  momlevel_amd passes it by default for the
                                global sums (mlx_steric_global*) only.  Denominators of exactly 0 / inf
                                / denormal size (never sea water) give NaN here, inf / 0 in numpy.  */
+#define MLX_FLAG_DRHO_F32 4 /* mlx_steric_local / mlx_steric_local_decomp: delta_rho_out points at
+                               FLOAT32 elements (nt,nz,plane); delta_rho_variant_stride counts
+                               float32 elements; 4-byte alignment suffices. eta_out is unchanged.
+                               Ignored when delta_rho_out is NULL; every other entry point refuses
+                               the bit (MLX_E_ENUM).                                              */
 #define MLX_FLAG_TCHUNK_MASK 0xFF00 /* K1 tuning hint, never changes a result: time steps per
                                block = 8 * ((flags >> 8) & 0xFF); 0 = the default (32)            */
 #define MLX_FLAG_TCHUNK(steps) ((((steps) / 8) & 0xFF) << 8)
@@ -252,6 +258,12 @@ int mlx_steric_global_decomp(const void *T, const void *S, const void *T0, const
  * evaluates calc_dz(levels, z_i, deptho) with its default top/bottom
  * (src/momlevel/derived.py:295-318) from z_i[nz+1] and deptho[plane] on the fly.
  * delta_rho_out may be NULL: the 8 B/cell store is then skipped.
+ * With MLX_FLAG_DRHO_F32 delta_rho_out holds FLOAT32 elements (the argument keeps its double*
+ * type, as mlx_eos_map_promote's out holds either by mode): each delta_rho value is rounded to
+ * float32 (to nearest even, what ndarray.astype(float32) does; NaN becomes the quiet NaN
+ * 0x7FC00000) immediately before its store -- 4 B/cell written instead of 8.  ONLY the stored
+ * field is rounded: eta is still the sum of the UNROUNDED float64 terms dz * delta_rho and is bit
+ * for bit what the call without the flag gives.
  * neg_inv_rhozero is (-1.0/rhozero) evaluated by the caller in float64.
  * ------------------------------------------------------------------------------- */
 int mlx_fold_mask(const double *rho0, const double *vol0, int64_t n,
@@ -273,7 +285,8 @@ int mlx_steric_local(const void *T, const void *S, int dtype,
  *   delta_rho_out + v*delta_rho_variant_stride   (nt,nz,plane)   [delta_rho_out may be NULL]
  *   eta_out       + v*eta_variant_stride         (nt,plane)
  * (strides in elements, >= the size of one field).  Each field is bit-identical to the
- * corresponding mlx_steric_local call.
+ * corresponding mlx_steric_local call.  MLX_FLAG_DRHO_F32: as there -- delta_rho_out and
+ * delta_rho_variant_stride are then in float32 elements (16 B read + 3 x 4 B written per cell).
  * ------------------------------------------------------------------------------- */
 int mlx_steric_local_decomp(const void *T, const void *S, const void *T0, const void *S0, int dtype,
                             const double *rho0m, const double *vol0_surface,

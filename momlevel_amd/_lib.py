@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("MOMLEVEL_AMD_LIB") or os.path.join(HERE, "libmomlevel
 _ORACLE_DIR = os.path.join(os.path.dirname(HERE), "oracle")
 
 # ---- constants mirrored from include/momlevel_hip.h --------------------------------
-ABI_VERSION = 8
+ABI_VERSION = 9
 EOS_WRIGHT, EOS_LINEAR = 0, 1
 FUNC_DENSITY, FUNC_DRHO_DTEMP, FUNC_DRHO_DSAL, FUNC_ALPHA, FUNC_BETA, FUNC_IBH = 0, 1, 2, 3, 4, 5
 FUNC_DENSITY_REF = 6  # eos.linear.density(..., rho_ref=x): mlx_eos_map_promote only
@@ -27,6 +27,7 @@ DTYPE_F64, DTYPE_F32, DTYPE_F32_UPCAST = 0, 1, 2
 DTYPE_T32_S64, DTYPE_T64_S32 = 3, 4  # theta / salinity of different dtypes (K1 / K2 only)
 FLAG_SKIP_DRY = 1
 FLAG_FMA = 2
+FLAG_DRHO_F32 = 4  # K2 only: delta_rho_out holds float32 elements (eta stays float64)
 BUILD_HIP, BUILD_HOST = 1, 2
 KIND_F64, KIND_F32, KIND_WEAK = 0, 1, 2  # operand kinds of mlx_eos_map_promote
 STRAT_N2, STRAT_TURNER = 0, 1  # mlx_stratification's func

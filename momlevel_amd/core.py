@@ -574,14 +574,27 @@ def fold_mask(rho0, vol0):
     return out
 
 
+def _delta_rho_dtype(delta_rho_dtype):
+    """``delta_rho_dtype`` of the K2 calls -> torch.float64 | torch.float32"""
+    if delta_rho_dtype in (None, torch.float64):
+        return torch.float64
+    if delta_rho_dtype == torch.float32:
+        return torch.float32
+    raise ValueError(f"delta_rho_dtype must be torch.float64 or torch.float32, not {delta_rho_dtype!r}")
+
+
 def _steric_local(entry, T, S, held, rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i, deptho, eos,
-                  f32_mode, skip_dry, arith):
+                  f32_mode, skip_dry, arith, delta_rho_dtype=torch.float64):
     """The operands both K2 entry points take (``held``: None, or the (T0, S0) of the all-variants
     launch), validated and on the device -> (device, (nt, nz, ny, nx), launch): ``launch(*outputs)``
-    enqueues ``entry`` with the output arguments that follow the common ones."""
+    enqueues ``entry`` with the output arguments that follow the common ones.
+    ``delta_rho_dtype`` torch.float32: MLX_FLAG_DRHO_F32 -- the delta_rho output (and its variant
+    stride) are in float32 elements."""
     require_device()
     T, S, nt, nz, ny, nx, sT, sS, dt, _ = _pair(T, S, f32_mode)
     flags = _launch_flags(skip_dry, arith, 0, "k2", dt)
+    if delta_rho_dtype == torch.float32:
+        flags |= _lib.FLAG_DRHO_F32
     dev = T.device
     if held is not None:
         held = _held_pair(entry, T, S, *held)
@@ -614,17 +627,29 @@ def _steric_local(entry, T, S, held, rho0m, vol0_surface, p, neg_inv_rhozero, dz
 
 def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=None,
                  deptho=None, eos="wright", f32_mode="faithful", want_delta_rho=True,
-                 delta_rho_out=None, eta_out=None, skip_dry=None, arith=None):
+                 delta_rho_out=None, eta_out=None, skip_dry=None, arith=None,
+                 delta_rho_dtype=torch.float64):
     """K2: (delta_rho (nt,nz,ny,nx) or None, eta (nt,ny,nx)).  ``skip_dry``, ``arith``: see
-    steric_global_masso.  ``p`` may be time dependent (4-D)."""
+    steric_global_masso.  ``p`` may be time dependent (4-D).
+    ``delta_rho_dtype`` torch.float32 (an extension; the default is float64): the kernel rounds each
+    delta_rho value to float32 right before storing it -- ``float32(float64 delta_rho)`` bit for
+    bit, half the bytes -- while eta is summed from the unrounded terms and stays float64, the
+    same bits as without it.  A ``delta_rho_out`` must be of that dtype."""
+    ddt = _delta_rho_dtype(delta_rho_dtype)
     dev, (nt, nz, ny, nx), launch = _steric_local(
         "mlx_steric_local", T, S, None, rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i, deptho,
-        eos, f32_mode, skip_dry, arith)
+        eos, f32_mode, skip_dry, arith, ddt if want_delta_rho else torch.float64)
     drho = None
     if want_delta_rho:
         drho = delta_rho_out
         if drho is None:
-            drho = torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=dev)
+            drho = torch.empty((nt, nz, ny, nx), dtype=ddt, device=dev)
+        elif (drho.dtype != ddt or drho.numel() < nt * nz * ny * nx or drho.device != dev
+              or not drho.is_contiguous()):
+            # (never a silent reinterpretation of the buffer's elements)
+            raise ValueError(f"delta_rho_out must be a contiguous {ddt} tensor of {(nt, nz, ny, nx)} "
+                             f"on {dev} (delta_rho_dtype={ddt}), not {drho.dtype} "
+                             f"{tuple(drho.shape)}")
     eta = eta_out if eta_out is not None else torch.empty(
         (nt, ny, nx), dtype=torch.float64, device=dev
     )
@@ -637,19 +662,22 @@ LOCAL_DECOMP_ROWS = ("steric", "thermosteric", "halosteric")
 
 def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=None,
                         deptho=None, eos="wright", f32_mode="faithful", want_delta_rho=True,
-                        delta_rho_out=None, eta_out=None, skip_dry=None, arith=None):
+                        delta_rho_out=None, eta_out=None, skip_dry=None, arith=None,
+                        delta_rho_dtype=torch.float64):
     """K2, all variants in one pass over theta/S: (delta_rho (3,nt,nz,ny,nx) or None,
     eta (3,nt,ny,nx)), variant order LOCAL_DECOMP_ROWS; each field bit-identical to its
     steric_local call.  ``delta_rho_out`` / ``eta_out``: optional (3, nt, ...) float64 device
-    tensors (or views whose variant axis has any stride, e.g. ``full[:, t0:t1]``)."""
+    tensors (or views whose variant axis has any stride, e.g. ``full[:, t0:t1]``).
+    ``delta_rho_dtype``: as in steric_local (``delta_rho_out`` then float32; eta stays float64)."""
+    ddt = _delta_rho_dtype(delta_rho_dtype)
     dev, (nt, nz, ny, nx), launch = _steric_local(
         "mlx_steric_local_decomp", T, S, (T0, S0), rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i,
-        deptho, eos, f32_mode, skip_dry, arith)
+        deptho, eos, f32_mode, skip_dry, arith, ddt if want_delta_rho else torch.float64)
 
-    def variant_major(x, shape):
-        """(3, nt, ...) float64 device tensor whose per-variant fields are contiguous"""
-        if tuple(x.shape) != shape or x.dtype != torch.float64 or x.device != dev:
-            raise ValueError(f"output must be a float64 {shape} tensor on {dev}")
+    def variant_major(x, shape, dtype=torch.float64):
+        """(3, nt, ...) device tensor of ``dtype`` whose per-variant fields are contiguous"""
+        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
+            raise ValueError(f"output must be a {dtype} {shape} tensor on {dev}")
         if not x[0].is_contiguous() or x.stride(0) < x[0].numel():
             raise ValueError("each variant's field must be contiguous")
         return x
@@ -657,8 +685,8 @@ def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, d
     drho = None
     if want_delta_rho:
         drho = delta_rho_out if delta_rho_out is not None else torch.empty(
-            (3, nt, nz, ny, nx), dtype=torch.float64, device=dev)
-        variant_major(drho, (3, nt, nz, ny, nx))
+            (3, nt, nz, ny, nx), dtype=ddt, device=dev)
+        variant_major(drho, (3, nt, nz, ny, nx), ddt)
     eta = eta_out if eta_out is not None else torch.empty((3, nt, ny, nx), dtype=torch.float64,
                                                            device=dev)
     variant_major(eta, (3, nt, ny, nx))

@@ -727,6 +727,7 @@ __device__ __forceinline__ void accumulate(double& c, double rho, double vol) {
 __device__ __forceinline__ double canonical_nan() {
   return __longlong_as_double(0x7FF8000000000000LL);
 }
+__device__ __forceinline__ float canonical_nan_f32() { return __int_as_float(0x7FC00000); }
 
 // splitmix64 -- synthetic-field generator; replayed in numpy by
 // momlevel_amd/synthetic.py

@@ -134,6 +134,26 @@ __device__ __forceinline__ void store_pack(double* __restrict__ p, const Pack<do
   }
 }
 
+// float32 packs (K2's narrowed delta_rho): one dword / dwordx2 / dwordx4 store per lane
+template <int VEC, bool STREAM = false>
+__device__ __forceinline__ void store_pack(float* __restrict__ p, const Pack<float, VEC>& r) {
+  if constexpr (VEC == 1) {
+    if constexpr (STREAM) __builtin_nontemporal_store(r.v[0], p);
+    else p[0] = r.v[0];
+  } else if constexpr (VEC == 2) {
+    double raw;
+    __builtin_memcpy(&raw, &r, 8);
+    if constexpr (STREAM) __builtin_nontemporal_store(raw, reinterpret_cast<double*>(p));
+    else *reinterpret_cast<double*>(p) = raw;
+  } else {
+    static_assert(VEC == 4, "float packs are 4, 8 or 16 bytes");
+    f4_t raw;
+    __builtin_memcpy(&raw, &r, 16);
+    if constexpr (STREAM) __builtin_nontemporal_store(raw, reinterpret_cast<f4_t*>(p));
+    else *reinterpret_cast<f4_t*>(p) = raw;
+  }
+}
+
 // 16 bytes per lane HBM -> LDS with no VGPR destination (global_load_lds_dwordx4 ... nt): lane l of
 // the wave writes lds_slice + 16*l, lds_slice being the wave's (uniform) 1 KiB slice.  Asynchronous:
 // counted by vmcnt; the data is in LDS after the caller's own s_waitcnt.  (The builtin exists in the
@@ -787,16 +807,23 @@ __device__ __forceinline__ double dz_default(double depth, double ztop, double z
 // NTI time steps live in LDS ([step][column][thread]: a wave's 64 lanes hit 64 consecutive doubles,
 // conflict-free; every thread owns its slots, no barrier) instead of VGPRs, so that one thread can
 // take 32 steps of one column -- north_star's "LDS-staged z-column tiles", VERDICT r4 next #5.
+// DRHO32 (MLX_FLAG_DRHO_F32): delta_rho_out holds FLOAT32 elements.  Each value is narrowed in
+// registers (v_cvt_f32_f64, round to nearest even: numpy's astype(float32)) right before its
+// non-temporal store -- 4 B/cell written instead of 8 -- AFTER dz * delta_rho has been taken from the
+// float64 value: the column sums, and with them eta, are bit for bit those of the float64 launch.
+// drho_vstride and the per-step offset count elements of the output type.
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GENERIC, bool SKIP, bool FMA,
-          bool P3D = false, bool LDSACC = false>
+          bool P3D = false, bool LDSACC = false, bool DRHO32 = false>
 __global__ __launch_bounds__(kBlock) void k_steric_local(
     const TIn* __restrict__ T, const TIn* __restrict__ S, const TIn* __restrict__ T0,
     const TIn* __restrict__ S0, const double* __restrict__ rho0m,
     const double* __restrict__ vol0_surface, const double* __restrict__ dz,
     const double* __restrict__ z_i, const double* __restrict__ deptho,
     const double* __restrict__ p, int p_mode, int eos, double neg_inv_rhozero, int nt, int nz,
-    int64_t plane, int64_t t_stride_T, int64_t t_stride_S, double* __restrict__ drho_out,
+    int64_t plane, int64_t t_stride_T, int64_t t_stride_S,
+    typename std::conditional<DRHO32, float, double>::type* __restrict__ drho_out,
     int64_t drho_vstride, double* __restrict__ eta_out, int64_t eta_vstride, int ntb_major) {
+  static_assert(!(DRHO32 && LDSACC), "the LDS column-sum experiment is eta-only");
   constexpr int NOUT = (VAR == kVarAll) ? 3 : 1;
   constexpr bool STREAM_T = (VAR != kVarHalo), STREAM_S = (VAR != kVarThermo);
   constexpr bool HELD_T = (VAR == kVarHalo || VAR == kVarAll);
@@ -986,29 +1013,49 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
           }
           quotients<Ops, NOUT * VEC>(&num[0][0], &den[0][0], &rho[0][0], pbad);
         }
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-#pragma unroll
-          for (int o = 0; o < NOUT; ++o) {
-            const double dr = rho[o][k] - r0.v[k];  // steric.py:152 (NaN where vol0 is NaN)
-            d[o].v[k] = dr;
-            const double term = dzv.v[k] * dr;          // steric.py:163
-            if constexpr (LDSACC) {
-              double c = sacc[(j * VEC + k) * kBlock + threadIdx.x];
-              add_skipna<PRED>(c, term);
-              sacc[(j * VEC + k) * kBlock + threadIdx.x] = c;
-            } else {
-              add_skipna<PRED>(acc[o][j][k], term);           // skipna, z ascending like numpy
-            }
+        // delta_rho of cell k of variant o (steric.py:152: NaN where vol0 is NaN).  Its term
+        // dz * delta_rho (steric.py:163) joins the column sum HERE, from the float64 value: the one
+        // place that defines eta, whatever becomes of delta_rho afterwards.
+        auto cell = [&](int o, int k) -> double {
+          const double dr = rho[o][k] - r0.v[k];
+          const double term = dzv.v[k] * dr;
+          if constexpr (LDSACC) {
+            double c = sacc[(j * VEC + k) * kBlock + threadIdx.x];
+            add_skipna<PRED>(c, term);
+            sacc[(j * VEC + k) * kBlock + threadIdx.x] = c;
+          } else {
+            add_skipna<PRED>(acc[o][j][k], term);  // skipna, z ascending like numpy
           }
-        }
-        if (drho_out != nullptr) {  // wave-uniform: the eta-only mode skips payload fix and store
+          return dr;
+        };
+        if constexpr (DRHO32) {
+          // (launched with a delta_rho output only: no eta-only mode.)  Variant by variant, each
+          // pack narrowed and stored as soon as it is complete: one v_cvt_f32_f64 per value (round
+          // to nearest even), canonical float32 NaN payload.
 #pragma unroll
           for (int o = 0; o < NOUT; ++o) {
+            Pack<float, VEC> f;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k)
-              d[o].v[k] = is_nan(d[o].v[k]) ? canonical_nan() : d[o].v[k];  // canonical payload
-            store_pack<VEC, true>(drho_out + o * drho_vstride + oD + off, d[o]);
+            for (int k = 0; k < VEC; ++k) {
+              const double dr = cell(o, k);
+              f.v[k] = is_nan(dr) ? canonical_nan_f32() : (float)dr;
+            }
+            store_pack<VEC, true>(drho_out + o * drho_vstride + oD + off, f);
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o) d[o].v[k] = cell(o, k);
+          }
+          if (drho_out != nullptr) {  // wave-uniform: the eta-only mode skips payload fix and store
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o) {
+#pragma unroll
+              for (int k = 0; k < VEC; ++k)
+                d[o].v[k] = is_nan(d[o].v[k]) ? canonical_nan() : d[o].v[k];  // canonical payload
+              store_pack<VEC, true>(drho_out + o * drho_vstride + oD + off, d[o]);
+            }
           }
         }
       }
@@ -1478,49 +1525,73 @@ struct K2Args {
   int p_mode, eos, nt, nz;
   double neg_inv_rhozero;
   int64_t plane, sT, sS;
-  double *drho, *eta;
+  void* drho;  // float64 elements, or float32 with drho32 (MLX_FLAG_DRHO_F32)
+  double* eta;
   int64_t drho_vstride, eta_vstride;
+  bool drho32;
   bool p3d;  // fast kernels: the pressure is a (z,y,x) field (template argument P3D)
   int ntb_major;  // > 0: 1-D grid, a tile's time blocks adjacent on one XCD (k_steric_local)
 };
 
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA,
-          bool P3D, bool LDSACC = false>
+          bool P3D, bool LDSACC = false, bool DRHO32 = false>
 void k2_launch(const K2Args& a) {
-  snprintf(g_kernel, sizeof(g_kernel), "k_steric_local<%s,%d,%d,%d,%d,%s,%s,%s%s%s>",
+  typedef typename std::conditional<DRHO32, float, double>::type TOut;
+  // (a float32-egress instantiation carries a trailing ",f32out": a profile row of it cannot be
+  //  taken for the float64 one)
+  snprintf(g_kernel, sizeof(g_kernel), "k_steric_local<%s,%d,%d,%d,%d,%s,%s,%s%s%s%s>",
            type_name<TIn>(), VEC, NTI, VAR, MODE, tf(GEN), tf(SKIP), tf(FMA),
-           (P3D || LDSACC) ? (P3D ? ",true" : ",false") : "", LDSACC ? ",lds" : "");
-  hipLaunchKernelGGL((k_steric_local<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, LDSACC>), a.grid,
-                     dim3(kBlock), 0, a.st, (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0,
-                     (const TIn*)a.S0, a.rho0m, a.surf, a.dz, a.z_i, a.deptho, a.p, a.p_mode, a.eos,
-                     a.neg_inv_rhozero, a.nt, a.nz, a.plane, a.sT, a.sS, a.drho, a.drho_vstride,
-                     a.eta, a.eta_vstride, a.ntb_major);
+           (P3D || LDSACC) ? (P3D ? ",true" : ",false") : "", LDSACC ? ",lds" : "",
+           DRHO32 ? ",f32out" : "");
+  hipLaunchKernelGGL(
+      (k_steric_local<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, LDSACC, DRHO32>), a.grid,
+      dim3(kBlock), 0, a.st, (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0, (const TIn*)a.S0,
+      a.rho0m, a.surf, a.dz, a.z_i, a.deptho, a.p, a.p_mode, a.eos, a.neg_inv_rhozero, a.nt, a.nz,
+      a.plane, a.sT, a.sS, (TOut*)a.drho, a.drho_vstride, a.eta, a.eta_vstride, a.ntb_major);
 }
 
-template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA>
-void k2_go(const K2Args& a) {
-  if constexpr (!GEN && VAR != kVarAll) {
-    if (a.p3d) {
-      k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, true>(a);
+// DR: which delta_rho egress this shape is launched with.  kDrBoth: float64 or float32 (the generic
+// twin and most all-variants kernels: one shape for everything); kDrF64: float64 or none (the
+// eta-only shapes of the single-variant fast kernels, which have a shape of their own for a
+// delta_rho output); kDrF32: float32 only -- a float32-egress twin exists only where it can run.
+constexpr int kDrF64 = 0, kDrBoth = 1, kDrF32 = 2;
+template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA, bool P3D,
+          int DR>
+void k2_out(const K2Args& a) {
+  if constexpr (DR != kDrF64) {
+    if (DR == kDrF32 || (a.drho32 && a.drho != nullptr)) {
+      k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, false, true>(a);
       return;
     }
   }
-  k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, false>(a);
+  if constexpr (DR != kDrF32) k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D>(a);
 }
 
-template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN>
+template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA,
+          int DR = kDrBoth>
+void k2_go(const K2Args& a) {
+  if constexpr (!GEN && VAR != kVarAll) {
+    if (a.p3d) {
+      k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, true, DR>(a);
+      return;
+    }
+  }
+  k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, false, DR>(a);
+}
+
+template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, int DR = kDrBoth>
 void k2_flags(const K2Args& a, bool skip, bool fma) {
   constexpr int FM = MODE;
   constexpr bool S1 = !GEN;
   if constexpr (IsMixed<MODE>::value) {  // exact arithmetic only
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false>(a);
-    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false>(a);
+    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false, DR>(a);
+    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false, DR>(a);
   } else if (fma) {
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, FM, GEN, S1, true>(a);
-    else k2_go<TIn, VEC, NTI, VAR, FM, GEN, false, true>(a);
+    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, FM, GEN, S1, true, DR>(a);
+    else k2_go<TIn, VEC, NTI, VAR, FM, GEN, false, true, DR>(a);
   } else {
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false>(a);
-    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false>(a);
+    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false, DR>(a);
+    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false, DR>(a);
   }
 }
 
@@ -1540,8 +1611,24 @@ void k2_single(const K2Args& a, bool skip, bool fma) {
       return;
     }
   }
+  // (one shape serves both where the two agree -- the float64 held-field passes: it then keeps its
+  //  float32-egress twin)
+  constexpr bool SAME = V0 == V1 && k2_nti(F64, VAR, true) == k2_nti(F64, VAR, false);
   if (a.drho != nullptr) k2_flags<TIn, V1, k2_nti(F64, VAR, true), VAR, MODE, false>(a, skip, fma);
-  else k2_flags<TIn, V0, k2_nti(F64, VAR, false), VAR, MODE, false>(a, skip, fma);
+  else k2_flags<TIn, V0, k2_nti(F64, VAR, false), VAR, MODE, false, SAME ? kDrBoth : kDrF64>(a, skip, fma);
+}
+
+// Time steps per thread of the all-variants kernel (kNTI64All / kNTI32All below) -- except with
+// float32 egress where the polynomial is float64 (float64 fields; float32 fields upcast): the float64-egress kernels sit at 246-253 VGPRs there, the narrowing costs 3-4 more (the
+// converted pack beside the value the column sum still needs, a second lane offset for 4-byte
+// elements), and past 256 the wave count per SIMD halves (scripts/isa_count.py: 254 VGPRs + 12
+// AGPRs at 8 steps).  Two steps fewer give 40 registers back.  Which thread sums which column in
+// which order of levels does not depend on it.
+#ifndef MLX_TUNE_NTI_ALL_F32OUT
+#define MLX_TUNE_NTI_ALL_F32OUT 6
+#endif
+constexpr int k2_nti_all_f32out(int mode, int nti) {
+  return (mode == kF64 || mode == kF32Upcast) ? MLX_TUNE_NTI_ALL_F32OUT : nti;
 }
 
 // NTI1: time steps per thread of the generic single-variant kernel (the fast ones: k2_nti);
@@ -1550,7 +1637,13 @@ void k2_single(const K2Args& a, bool skip, bool fma) {
 template <typename TIn, int VEC, int NTI1, int VEC3, int NTI3, int MODE, bool GEN>
 void k2_var(const K2Args& a, int var, bool skip, bool fma) {
   if (var == kVarAll) {
-    k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN>(a, skip, fma);
+    constexpr int NTI3F = GEN ? NTI3 : k2_nti_all_f32out(MODE, NTI3);  // (its own time block: there)
+    if constexpr (NTI3F != NTI3) {
+      if (a.drho32 && a.drho != nullptr) k2_flags<TIn, VEC3, NTI3F, kVarAll, MODE, GEN, kDrF32>(a, skip, fma);
+      else k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN, kDrF64>(a, skip, fma);
+    } else {
+      k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN>(a, skip, fma);
+    }
   } else if constexpr (GEN) {  // held fields reach the generic twin as stride-0 streams
     k2_flags<TIn, VEC, NTI1, kVarSteric, MODE, GEN>(a, skip, fma);
   } else {
@@ -1570,10 +1663,13 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
                       int dtype, const double* rho0m, const double* vol0_surface, const double* dz,
                       const double* z_i, const double* deptho, const double* p, int p_mode, int eos,
                       double neg_inv_rhozero, int64_t nt, int64_t nz, int64_t plane, int64_t sT,
-                      int64_t sS, int flags, double* delta_rho_out, int64_t drho_vstride,
+                      int64_t sS, int flags, void* delta_rho_out, int64_t drho_vstride,
                       double* eta_out, int64_t eta_vstride, void* stream) {
-  if (flags & ~(MLX_FLAG_SKIP_DRY | MLX_FLAG_FMA)) return fail(MLX_E_ENUM, "unknown flag bits");
+  if (flags & ~(MLX_FLAG_SKIP_DRY | MLX_FLAG_FMA | MLX_FLAG_DRHO_F32))
+    return fail(MLX_E_ENUM, "unknown flag bits");
   const bool skip = (flags & MLX_FLAG_SKIP_DRY) != 0, fma = (flags & MLX_FLAG_FMA) != 0;
+  // float32 delta_rho elements (ignored without a delta_rho output)
+  const bool drho32 = (flags & MLX_FLAG_DRHO_F32) != 0 && delta_rho_out != nullptr;
   if (int rc = check_common(T, S, dtype, p, p_mode, eos, nt, nz, plane, sT, sS, true)) return rc;
   if (mixed_dtype(dtype) && fma)
     return fail(MLX_E_ENUM, "MLX_FLAG_FMA is not available for theta/salinity of different dtypes");
@@ -1582,9 +1678,11 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
   if (!dz && (!z_i || !deptho))
     return fail(MLX_E_NULL, "either dz or both z_i and deptho must be given");
   for (const void* q : {(const void*)rho0m, (const void*)vol0_surface, (const void*)dz,
-                        (const void*)z_i, (const void*)deptho, (const void*)delta_rho_out,
-                        (const void*)eta_out})
+                        (const void*)z_i, (const void*)deptho,
+                        drho32 ? nullptr : (const void*)delta_rho_out, (const void*)eta_out})
     if (q && !aligned(q, 8)) return fail(MLX_E_ALIGN, "operands not 8-byte aligned");
+  if (drho32 && !aligned(delta_rho_out, 4))
+    return fail(MLX_E_ALIGN, "float32 delta_rho_out not 4-byte aligned");
   if (var == kVarAll) {
     if (!T0 || !S0) return fail(MLX_E_NULL, "T0 and S0 must not be NULL");
     if (!aligned(T0, elem_size(dtype, true)) || !aligned(S0, elem_size(dtype, false)))
@@ -1619,6 +1717,13 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
                              : vec_of(dtype);
   int nti = (var == kVarAll) ? (fast ? (f64 ? kNTI64All : kNTI32All) : kNTIGenAll)
                              : (fast ? k2_nti(f64, var, delta_rho_out != nullptr) : kNTIGen);
+  if (var == kVarAll && fast && drho32)  // (the float32-egress shape of the float64 polynomial)
+    nti = k2_nti_all_f32out(dtype == MLX_DTYPE_F64          ? kF64
+                            : dtype == MLX_DTYPE_F32_UPCAST ? kF32Upcast
+                            : dtype == MLX_DTYPE_F32        ? kF32Faithful
+                            : dtype == MLX_DTYPE_T32_S64    ? kMixT32
+                                                            : kMixS32,
+                            nti);
   if (MLX_TUNE_K2_LDSACC && fast && (var == kVarHalo || var == kVarThermo) && !delta_rho_out &&
       !skip && !fma && p_mode != MLX_P_FULL3D &&
       (dtype == MLX_DTYPE_F64 || dtype == MLX_DTYPE_F32)) {  // (the experiment's shape: k2_single)
@@ -1647,6 +1752,7 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
   a.deptho = deptho; a.p = p ? p : rho0m; a.p_mode = p_mode; a.eos = eos; a.nt = (int)nt;
   a.nz = (int)nz; a.neg_inv_rhozero = neg_inv_rhozero; a.plane = plane; a.sT = sT; a.sS = sS;
   a.drho = delta_rho_out; a.eta = eta_out; a.drho_vstride = drho_vstride; a.eta_vstride = eta_vstride;
+  a.drho32 = drho32;
   a.p3d = fast && p_mode == MLX_P_FULL3D;
   if (fast) {
     if (dtype == MLX_DTYPE_T32_S64)

@@ -331,12 +331,23 @@ def sum_dtype(x):
 # ---------------------------------------------------------------------------------------
 # local variant (src/momlevel/steric.py:150-166)
 # ---------------------------------------------------------------------------------------
-def _host_output(shape):
-    """float64 host array for results copied back from the device, filled through the staging ring:
-    a huge-page mapping of our own when large (pooled across calls, hostio._ResultPool), an ordinary
-    numpy array when small, page-locked memory when the caller opted in; see
-    hostio.result_array."""
-    return hostio.result_array(shape, np.float64)
+def _host_output(shape, dtype=np.float64):
+    """host array (float64; float32 for an opted-in delta_rho) for results copied back from the
+    device, filled through the staging ring: a huge-page mapping of our own when large (pooled
+    across calls, hostio._ResultPool), an ordinary numpy array when small, page-locked memory when
+    the caller opted in; see hostio.result_array."""
+    return hostio.result_array(shape, dtype)
+
+
+def _narrowed(x):
+    """float32(x) of a float64 result, host array or device tensor (round to nearest even).
+    Only the annual MEANS come here -- 1/12 of the record, after the float64 mean has been taken by
+    mlx_group_weighted_mean.  A host result is narrowed on the host.  A device-resident one is
+    narrowed by a torch dtype cast: the one place on this path where torch touches values on the
+    device, and a deliberate exception -- mlx_group_weighted_mean's prototype has no flags argument
+    to ask its store for float32 and this ABI version adds no symbol; the cast is the same single
+    IEEE round-to-nearest-even conversion (tests/test_gpu_delta_rho_f32.py, annual, resident)."""
+    return x.to(torch.float32) if isinstance(x, torch.Tensor) else x.astype(np.float32)
 
 
 # ---------------------------------------------------------------------------------------
@@ -423,7 +434,7 @@ def _local_operands(T, S, rho0, vol0, pres, rhozero, z_i, deptho, dz, out_host):
 def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i=None,
                           deptho=None, dz=None, eos="wright", f32_mode="faithful",
                           want_delta_rho=True, out_host=None, steps=None, annual_weights=None,
-                          reference_is_step0=False):
+                          reference_is_step0=False, delta_rho_dtype=None):
     """{variant: (delta_rho, eta)}; theta/S chunks are uploaded once and reused.
 
     ``out_host=True`` returns numpy arrays filled chunk by chunk (for host inputs larger than
@@ -433,7 +444,14 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
     1/12 of delta_rho / eta is ever stored or copied back; the outputs are (nt/12, ...).
     ``reference_is_step0``: (T0, S0) ARE time level 0 of (T, S) -- a reference state steric() made
     itself: the first chunk of a host record is then that step, taken from the device.
+    ``delta_rho_dtype`` torch.float32 (an extension; None / torch.float64: the default): every
+    delta_rho field is ``float32(float64 delta_rho)`` -- K2 narrows each value right before its store,
+    so device buffers, downloads and host results of that field are half the size; eta is summed
+    from the unrounded terms and is the same float64 bits either way.  Annual means are taken over
+    the float64 field on the device, as without it, and the MEAN is narrowed: never a mean of
+    rounded values.
     """
+    drho32 = want_delta_rho and core._delta_rho_dtype(delta_rho_dtype) == torch.float32
     dev, pres, out_host, (rho0m, surface, neg_inv), depth = _local_operands(
         T, S, rho0, vol0, pres, rhozero, z_i, deptho, dz, out_host)
     T0 = to_device(T0, dev, _stream_dtype(T0))
@@ -441,7 +459,11 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
     nz, ny, nx = tuple(rho0m.shape)
     nt = T.shape[0]
     annual = annual_weights is not None
-    extra = len(variants) * nz * ny * nx * 8 if (want_delta_rho and (out_host or annual)) else 0
+    # what K2 itself stores: float32 on request -- except ahead of the annual mean (see above)
+    kernel_dtype = torch.float32 if (drho32 and not annual) else torch.float64
+    drho_bytes = 4 if kernel_dtype == torch.float32 else 8
+    extra = (len(variants) * nz * ny * nx * drho_bytes
+             if (want_delta_rho and (out_host or annual)) else 0)
     extra += _pressure_bytes_per_step(pres)
     Ts, Ss = _streamed_pair(variants, T, S, T0, S0)
     if annual:
@@ -460,9 +482,10 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
                         first_step=(T0, S0) if reference_is_step0 else None)
     nt_out = nt // 12 if annual else nt
 
-    def alloc(shape):
-        return _host_output(shape) if out_host else torch.empty(shape, dtype=torch.float64,
-                                                                device=dev)
+    def alloc(shape, dtype=torch.float64):
+        if out_host:
+            return _host_output(shape, np.float32 if dtype == torch.float32 else np.float64)
+        return torch.empty(shape, dtype=dtype, device=dev)
 
     # all three variants of a 4-D record: ONE pass of the all-variants kernel per chunk (theta/S
     # read once: 16 B read + 3 x 8 B written per cell instead of 56 B); every field bit-identical
@@ -473,15 +496,17 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
     direct = one_pass and not out_host and not annual  # the kernel writes the final tensors
     if direct:
         eta_all = torch.empty((3, nt, ny, nx), dtype=torch.float64, device=dev)
-        drho_all = (torch.empty((3, nt, nz, ny, nx), dtype=torch.float64, device=dev)
+        drho_all = (torch.empty((3, nt, nz, ny, nx), dtype=kernel_dtype, device=dev)
                     if want_delta_rho else None)
         eta = {v: eta_all[i] for i, v in enumerate(rows)}
         drho = {v: (drho_all[i] if want_delta_rho else None) for i, v in enumerate(rows)}
     else:
         eta = {v: alloc((nt_out, ny, nx)) for v in variants}
-        drho = {v: (alloc((nt_out, nz, ny, nx)) if want_delta_rho else None) for v in variants}
+        drho = {v: (alloc((nt_out, nz, ny, nx), kernel_dtype) if want_delta_rho else None)
+                for v in variants}
     in_place = not out_host and not annual  # per-variant launches write the device outputs too
-    kw = dict(depth, eos=eos, f32_mode=f32_mode, want_delta_rho=want_delta_rho)
+    kw = dict(depth, eos=eos, f32_mode=f32_mode, want_delta_rho=want_delta_rho,
+              delta_rho_dtype=kernel_dtype)
 
     # host results leave on a stream and a worker thread of their own (hostio.Downloader): the D2H
     # of chunk k overlaps the H2D of chunk k+1 and this loop goes straight on to chunk k+1's kernels
@@ -522,4 +547,6 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
                         going_out.append((drho[v][o0:o1], d))
             if going_out:
                 results.submit(going_out)
+    if drho32 and annual:  # the float64 means (1/12 of the record) are complete here: narrow them
+        drho = {v: _narrowed(d) for v, d in drho.items()}
     return {v: (drho[v], eta[v]) for v in variants}

@@ -18,6 +18,7 @@ import contextlib
 import os
 
 import numpy as np
+import torch
 
 from . import engine
 from .adapters import accepts_xarray
@@ -61,6 +62,38 @@ def _check_dz_inputs(levels, interfaces, depth):
     assert bool(np.all(interfaces.values >= 0)), (
         "Vertical coordinate interfaces must all be positive-definite"
     )
+
+
+# EXTENSION (not in momlevel), opt-in: the in-memory dtype of ``delta_rho``.  The reference computes
+# the field in float64 and tags it encoding["dtype"] = dtype (steric.py:27,160: "float32" unless
+# the caller says otherwise), so every file written from it holds float32.  "encoding" materialises
+# the field in the dtype its own encoding names when that is float32: K2 rounds each value once,
+# to nearest even, right before storing it (= ``delta_rho.astype("float32")`` of the float64
+# field), and everything downstream moves half the bytes.  The height field is summed from the
+# unrounded terms and stays float64, bit for bit what the default gives.
+_DELTA_RHO_DTYPES = ("float64", "encoding")
+
+
+def delta_rho_dtype_for(dtype, delta_rho_dtype=None, environ=None):
+    """-> "float64" | "float32": what ``delta_rho`` is materialised as.  ``delta_rho_dtype``: None
+    (then the environment's MOMLEVEL_AMD_DELTA_RHO_DTYPE decides; default "float64"), "float64" or
+    "encoding" -- float32 when ``dtype`` (steric()'s encoding argument) names float32, float64 for
+    anything else.  A keyword wins over the environment; unknown values are refused."""
+    if delta_rho_dtype is None:
+        environ = os.environ if environ is None else environ
+        choice, where = environ.get("MOMLEVEL_AMD_DELTA_RHO_DTYPE", "float64"), "MOMLEVEL_AMD_DELTA_RHO_DTYPE"
+    else:
+        choice, where = delta_rho_dtype, "delta_rho_dtype"
+    if choice not in _DELTA_RHO_DTYPES:
+        raise ValueError(f"{where} must be one of {', '.join(map(repr, _DELTA_RHO_DTYPES))}, "
+                         f"not {choice!r}")
+    if choice == "float64":
+        return "float64"
+    try:
+        named = np.dtype(dtype)
+    except TypeError:
+        return "float64"  # (an encoding numpy cannot name: nothing to follow)
+    return "float32" if named == np.dtype(np.float32) else "float64"
 
 
 # EXTENSION (not in momlevel): ocean heat content beside the steric decomposition
@@ -128,10 +161,11 @@ def _global_results(ops, reference, variants, dtype, tcoord, coords_for, deferre
 
 
 def _local_results(ops, dset, rho0, variants, dtype, rhozero, names, cdims3, coords_for,
-                   plan=None, reference_is_step0=False):
+                   plan=None, reference_is_step0=False, delta_rho_dtype=None):
     """steric.py:150-166 -- delta_rho and the column integral from K2.  ``rho0``: the reference
     state's density in canonical (z,y,x) order.  ``plan`` (an util.AnnualPlan): the annual means
-    are taken on the device, fused behind K2."""
+    are taken on the device, fused behind K2.  ``delta_rho_dtype``: torch.float32 for the opted-in
+    float32 field (delta_rho_dtype_for), None for the default."""
     T, S, T0, S0, vol0, p, eos = ops
     tcoord, zcoord, zbounds = names
     hdims = cdims3[1:]
@@ -145,7 +179,7 @@ def _local_results(ops, dset, rho0, variants, dtype, rhozero, names, cdims3, coo
         T, S, T0, S0, rho0, vol0, p, rhozero, variants,
         z_i=dset[zbounds].data, deptho=deptho.data, eos=eos, f32_mode=_f32_mode(),
         want_delta_rho=want_delta_rho, annual_weights=None if plan is None else plan.weights,
-        reference_is_step0=reference_is_step0,
+        reference_is_step0=reference_is_step0, delta_rho_dtype=delta_rho_dtype,
     )
     def result_coords(dims):
         coords = coords_for(dims)
@@ -236,14 +270,16 @@ def _steric_many(*args, **kwargs):
 
 def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rhozero, patm,
                  equation_of_state, domain, dtype, strict, annual, verbose, heat_cp=None,
-                 exchange=None):
+                 exchange=None, delta_rho_dtype=None):
     """The body of steric() for one or several variants sharing one reference state and one
     pass of theta/S through the device.  Returns ({variant: result}, reference).
     ``twins``: the caller's dict for the device tensors of a self-made reference state (and its
     pending rho0 download).
     ``exchange``: None, or -- when ``dset`` is ONE RANK'S horizontal tile of a multi-GPU run
     (momlevel_amd.parallel.steric) -- a callable summing a float64 vector over the ranks; the
-    global sums (sum of areacello, volo, masso) then go through it, everything else is local."""
+    global sums (sum of areacello, volo, masso) then go through it, everything else is local.
+    ``delta_rho_dtype``: see delta_rho_dtype_for (None: the environment decides)."""
+    drho32 = delta_rho_dtype_for(dtype, delta_rho_dtype) == "float32"  # (refuses junk before any work)
     dset = dset.rename(varname_map)
     names = default_coords(coord_names)
     tcoord, zcoord, zbounds = names
@@ -316,6 +352,7 @@ def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rho
         equation_of_state.lower(),
     )
     plan = None
+    narrow_late = False
     if annual and domain != "global":
         plan = AnnualPlan(dset[tcoord], tcoord)  # asserts 12 steps per year (util.py:85)
         if not plan.contiguous:
@@ -328,8 +365,12 @@ def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rho
         if heat_cp is not None:
             raise ValueError("heat_content is a global integral: use domain='global'")
         # (twins: the reference state was made in this call from time level 0 of this record)
+        # an annual mean taken afterwards on the host (no plan) averages the float64 field too:
+        # delta_rho is narrowed behind it, below -- never a mean of rounded values
+        narrow_late = drho32 and annual and plan is None
         results = _local_results(ops, dset, slab("rho"), variants, dtype, rhozero, names, cdims3,
-                                 coords_for, plan, reference_is_step0="thetao" in twins)
+                                 coords_for, plan, reference_is_step0="thetao" in twins,
+                                 delta_rho_dtype=torch.float32 if drho32 and not narrow_late else None)
 
     for variant, result in results.items():
         if variant == "heat":
@@ -346,6 +387,9 @@ def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rho
                 result[var].attrs.update(dset[var].attrs)
         if annual and plan is None:
             results[variant] = annual_average(result)
+            if narrow_late and "delta_rho" in results[variant].variables:
+                field = results[variant]["delta_rho"]
+                field.data = engine._narrowed(field.data)
     return results, reference
 
 
@@ -381,7 +425,9 @@ def steric(
     equation_of_state : str -- a module of ``momlevel_amd.eos`` ("Wright", "linear")
     variant : "steric" | "thermosteric" | "halosteric"
     domain : "local" (column integral per grid point) | "global" (one value per time step)
-    dtype : str -- output ENCODING metadata only; the arithmetic is float64
+    dtype : str -- output ENCODING metadata only; the arithmetic is float64 (with the opt-in
+        MOMLEVEL_AMD_DELTA_RHO_DTYPE=encoding -- not reference behaviour -- ``delta_rho`` alone is
+        also MATERIALISED as float32 when this names float32: delta_rho_dtype_for)
     strict : bool -- False downgrades the areacello range check to a warning
     annual : bool -- days-in-month weighted annual means of the result
     verbose : bool
@@ -414,6 +460,7 @@ def steric_variants(
     verbose=False,
     heat_content=False,
     cp=OHC_CP,
+    delta_rho_dtype=None,
 ):
     """EXTENSION (not in momlevel): several variants in one call.
 
@@ -425,6 +472,10 @@ def steric_variants(
     (theta/S read once).  ``heat_content=True`` (global only) adds ``results["heat"]["ohc"]``, the
     ocean heat content ``rhozero * cp * sum(thetao * volcello_ref)`` per time step from the same
     pass -- an extension with no counterpart in momlevel.
+    ``delta_rho_dtype`` (local domain): None | "float64" | "encoding" -- "encoding" materialises each
+    ``delta_rho`` in the dtype its ``encoding["dtype"]`` names when that is float32 (the default
+    ``dtype`` argument), i.e. ``float32(float64 delta_rho)``; the height fields are unchanged.  None
+    leaves the choice to MOMLEVEL_AMD_DELTA_RHO_DTYPE (default "float64"); see delta_rho_dtype_for.
 
     Returns
     -------
@@ -433,7 +484,7 @@ def steric_variants(
     results, reference = _steric_many(
         dset, tuple(variants), reference, coord_names, varname_map, rhozero, patm,
         equation_of_state, domain, dtype, strict, annual, verbose,
-        heat_cp=cp if heat_content else None,
+        heat_cp=cp if heat_content else None, delta_rho_dtype=delta_rho_dtype,
     )
     return (results, reference)
 

@@ -6,7 +6,10 @@ numpy-backed inputs of that shape (synthetic fields), wall-clock including the P
 ways.  (bench.py runs this with a checker that holds one time step against the numpy oracle and
 times the oracle on it; the script by itself only times the product.)
 
-    python scripts/example_call.py [--nt 60] [--nz 35]
+    python scripts/example_call.py [--nt 60] [--nz 35] [--delta-rho-dtype encoding]
+
+``--delta-rho-dtype encoding`` (an extension, MOMLEVEL_AMD_DELTA_RHO_DTYPE): delta_rho comes back in
+the float32 its encoding names -- half the bytes of the binding, download direction.
 """
 import argparse
 import json
@@ -23,8 +26,11 @@ from momlevel_amd import core, hostio, synthetic  # noqa: E402
 from momlevel_amd.labeled import DataArray, Dataset  # noqa: E402
 
 
-def run(nt=60, nz=35, reps=2, ny=1080, nx=1440, checker=None, before_call=None, source="numpy"):
-    """``source``: how thetao / so are held -- "numpy" (plain arrays), "masked" (numpy masked arrays
+def run(nt=60, nz=35, reps=2, ny=1080, nx=1440, checker=None, before_call=None, source="numpy",
+        delta_rho_dtype=None):
+    """``delta_rho_dtype``: None (whatever the environment says: float64 by default), "float64" or
+    "encoding" -- MOMLEVEL_AMD_DELTA_RHO_DTYPE for the duration of the calls.
+    ``source``: how thetao / so are held -- "numpy" (plain arrays), "masked" (numpy masked arrays
     with 1e20 under the mask: an in-memory netCDF4 read) or "masked_lazy" (read slice by slice, every
     slice a masked array: a netCDF4.Variable; tests/lazy_array.py)."""
     g = synthetic.make_grid(ny, nx, nz)
@@ -67,35 +73,51 @@ def run(nt=60, nz=35, reps=2, ny=1080, nx=1440, checker=None, before_call=None, 
     d["areacello"] = DataArray(g["areacello"].astype(np.float32), ("yh", "xh"))
     d["deptho"] = DataArray(g["deptho"], ("yh", "xh"))
     cells = nt * nz * ny * nx
+    from momlevel_amd.steric import delta_rho_dtype_for
+
+    out_dtype = np.dtype(delta_rho_dtype_for("float32", delta_rho_dtype))  # (thermosteric's default)
+    saved = os.environ.get("MOMLEVEL_AMD_DELTA_RHO_DTYPE")
+    if delta_rho_dtype is not None:
+        os.environ["MOMLEVEL_AMD_DELTA_RHO_DTYPE"] = delta_rho_dtype
     out = {"call": "thermosteric(ds)  # domain='local', float32 thetao/so from host memory, delta_rho returned",
            "source": source,
            "shape_t_z_y_x": list(shape), "cells": cells,
            "host_bytes_in_GB": round(2 * cells * 4 / 1e9, 2),
-           "host_bytes_out_GB": round((cells + nt * ny * nx) * 8 / 1e9, 2)}
+           "host_bytes_out_GB": round((cells * out_dtype.itemsize + nt * ny * nx * 8) / 1e9, 2),
+           "delta_rho_dtype": out_dtype.name}
     if source != "numpy":
         out["DataArray_construction_s"] = round(wrap_s, 3)
     walls = []
     res = ref = drho = eta = None
-    for _ in range(reps):
-        del res, ref, drho, eta  # (freeing 27 GB of earlier results is the caller's time, not the call's)
-        import gc
+    try:
+        for _ in range(reps):
+            del res, ref, drho, eta  # (freeing 27 GB of earlier results is the caller's time, not the call's)
+            import gc
 
-        gc.collect()
-        if before_call is not None:
-            before_call()
-        t0 = time.perf_counter()
-        with hostio.roctx_range("thermosteric(ds) on host float32 inputs"):  # (MOMLEVEL_AMD_ROCTX=1)
-            res, ref = m.thermosteric(d)
-            drho = res["delta_rho"].values  # host arrays: the call has synchronised
-            eta = res["thermosteric"].values
-        walls.append(time.perf_counter() - t0)
-        assert drho.shape == shape and eta.shape == (nt, ny, nx) and drho.dtype == np.float64
+            gc.collect()
+            if before_call is not None:
+                before_call()
+            t0 = time.perf_counter()
+            with hostio.roctx_range("thermosteric(ds) on host float32 inputs"):  # (MOMLEVEL_AMD_ROCTX=1)
+                res, ref = m.thermosteric(d)
+                drho = res["delta_rho"].values  # host arrays: the call has synchronised
+                eta = res["thermosteric"].values
+            walls.append(time.perf_counter() - t0)
+            assert drho.shape == shape and eta.shape == (nt, ny, nx) and drho.dtype == out_dtype
+    finally:  # (whatever happened in there: the process environment is the caller's)
+        if delta_rho_dtype is not None:
+            if saved is None:
+                del os.environ["MOMLEVEL_AMD_DELTA_RHO_DTYPE"]
+            else:
+                os.environ["MOMLEVEL_AMD_DELTA_RHO_DTYPE"] = saved
     out["wall_s"] = [round(w, 3) for w in walls]
     best = min(walls)
     out["Mcells/s_end_to_end"] = round(cells / best / 1e6, 1)
     # thermosteric streams theta only (S is held at the reference state: one slab)
     out["host_bytes_streamed_in_GB"] = round(cells * 4 / 1e9, 2)
-    out["GB/s_host_link_in_plus_out"] = round((cells * 4 + (cells + nt * ny * nx) * 8) / best / 1e9, 1)
+    link_bytes = cells * 4 + cells * out_dtype.itemsize + nt * ny * nx * 8
+    out["link_bytes"] = link_bytes
+    out["GB/s_host_link_in_plus_out"] = round(link_bytes / best / 1e9, 1)
     if checker is not None:  # bench.py's CPU leg: the oracle on one step of the same call
         out.update(checker(host, g, drho, eta, best))
     return out
@@ -107,8 +129,10 @@ def main():
     ap.add_argument("--nz", type=int, default=35)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--source", choices=["numpy", "masked", "masked_lazy", "masked_onecell"], default="numpy")
+    ap.add_argument("--delta-rho-dtype", choices=["float64", "encoding"], default=None)
     a = ap.parse_args()
-    print(json.dumps(run(a.nt, a.nz, a.reps, source=a.source)), flush=True)
+    print(json.dumps(run(a.nt, a.nz, a.reps, source=a.source, delta_rho_dtype=a.delta_rho_dtype)),
+          flush=True)
 
 
 if __name__ == "__main__":

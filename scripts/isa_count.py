@@ -75,7 +75,7 @@ def classify(lines):
     blocks that carry the kernels' asm marker, eos_device.hpp quotients<>) are left out and
     counted as `cold`"""
     c = dict(valu=0, f64=0, pk=0, trans=0, cndmask=0, cmp=0, mov=0, vmem=0, salu=0, lds=0, cvt=0,
-             cold=0)
+             cold=0, lane=0)
     blocks, cur = [], []
     for line in lines:
         if re.match(r"^\.LBB\w+:", line) or re.match(r"^; %bb\.\d+:", line):
@@ -109,6 +109,8 @@ def classify(lines):
                     c["mov"] += 1
                 if op.startswith("v_cvt"):
                     c["cvt"] += 1
+                if op.startswith(("v_writelane", "v_readlane")):  # SGPRs spilled into VGPR lanes
+                    c["lane"] += 1
             elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
                 c["vmem"] += 1
             elif op.startswith("ds_"):
@@ -163,7 +165,7 @@ def main():
         short = re.sub(r"^void mlx::", "", p).split("(")[0]
         print(f"{short:72s} loop VALU {c['valu']:4d} (f64 {c['f64']:3d} pk {c['pk']:3d} trans {c['trans']:2d} "
               f"cnd {c['cndmask']:3d} cmp {c['cmp']:3d} mov {c['mov']:3d} cvt {c['cvt']:3d}) "
-              f"vmem {c['vmem']:2d} salu {c['salu']:3d} lds {c['lds']:2d} cold {c['cold']:3d} | vgpr {m.get('NumVgprs')} "
+              f"vmem {c['vmem']:2d} salu {c['salu']:3d} lds {c['lds']:2d} lane {c['lane']:3d} cold {c['cold']:3d} | vgpr {m.get('NumVgprs')} "
               f"agpr {m.get('NumAgprs')} occ {m.get('Occupancy')} scratch {m.get('ScratchSize')}")
         if a.dump and a.dump in p:
             print("\n".join(body[best[0]:best[1] + 1]))
