@@ -2,9 +2,10 @@
 
 A drop-in for one path of jkrasting/momlevel: the Wright (1997) in-situ density and
 the volume-weighted reductions behind ``steric`` / ``halosteric`` / ``thermosteric``
-and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, computed by hand-written
-HIP kernels behind a C ABI (include/momlevel_hip.h).  Everything else in momlevel
-(trends, tide gauges, vorticity, spiciness, ...) is out of scope -- use momlevel.
+and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, and the per-cell trend,
+detrend and deseason fits of ``trend``, computed by hand-written HIP kernels behind a
+C ABI (include/momlevel_hip.h, include/momlevel_trend.h).  Everything else in momlevel
+(tide gauges, vorticity, spiciness, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
 entry points raise ``MomlevelHipError``.
@@ -17,11 +18,17 @@ from . import dynamic
 from . import eos
 from . import reference
 from . import test_data
+from . import timeseries_data
+from . import trend
 from . import util
 from ._lib import MomlevelHipError
 from .dynamic import inverse_barometer
 from .labeled import DataArray, Dataset
 from .steric import halosteric, steric, steric_variants, thermosteric
+
+# the reference keeps generate_test_data_time in its test_data module; the version with the
+# ``frequency`` argument ("MS" | "D") lives in timeseries_data and is published there
+test_data.generate_test_data_time = timeseries_data.generate_test_data_time
 
 __all__ = [
     "DataArray",
@@ -37,5 +44,6 @@ __all__ = [
     "steric_variants",
     "test_data",
     "thermosteric",
+    "trend",
     "util",
 ]

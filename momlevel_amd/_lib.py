@@ -31,6 +31,10 @@ FLAG_DRHO_F32 = 4  # K2 only: delta_rho_out holds float32 elements (eta stays fl
 BUILD_HIP, BUILD_HOST = 1, 2
 KIND_F64, KIND_F32, KIND_WEAK = 0, 1, 2  # operand kinds of mlx_eos_map_promote
 STRAT_N2, STRAT_TURNER = 0, 1  # mlx_stratification's func
+# ---- constants mirrored from include/momlevel_trend.h ------------------------------
+TREND_MAX_TERMS = 8
+(APPLY_REMOVE, APPLY_CORRECT, APPLY_TREND, APPLY_TREND_ANOM, APPLY_MODEL_RESID,
+ APPLY_MODEL) = range(6)
 
 
 def flag_tchunk(steps):
@@ -118,6 +122,17 @@ SIGNATURES = {
 }
 
 
+# The trend entry points (include/momlevel_trend.h): a table of their own, bound by load_trend() on
+# first use -- SIGNATURES stays the set include/momlevel_hip.h declares, which every build of that
+# ABI (the checker's host restatement, the sanitized build) exports.
+TREND_SIGNATURES = {
+    "mlx_time_fit_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "mlx_time_linfit": (_int, [_vp, _int, _vp, _i64, _i64, _dbl, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "mlx_time_project": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "mlx_time_apply": (_int, [_vp, _int, _int, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -161,6 +176,29 @@ def load():
             f"({BUILD_HIP}): momlevel_amd has no CPU backend"
         )
     _lib = lib
+    return lib
+
+
+_trend_bound = False
+
+
+def load_trend():
+    """load(), then declare the prototypes of include/momlevel_trend.h (once); a library built
+    without csrc/momlevel_trend.hip raises ``MomlevelHipError``."""
+    global _trend_bound
+    lib = load()
+    if _trend_bound:
+        return lib
+    for name, (restype, argtypes) in TREND_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise MomlevelHipError(
+                f"{LIB_PATH} does not export {name}: rebuild it with the trend kernels "
+                "(`python -m momlevel_amd.csrc.build --force`)") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _trend_bound = True
     return lib
 
 

@@ -1,4 +1,4 @@
-"""The few calendar facts ``annual_average`` and the test-data time axes need.
+"""The few calendar facts ``annual_average``, the trend module and the test-data time axes need.
 
 The reference uses cftime (absent from this image).  ``DatetimeLite`` exposes
 the attributes momlevel reads from a ``cftime.datetime`` -- ``year``, ``month``,
@@ -7,6 +7,9 @@ sit in a time coordinate handed to ``util.annual_average``.
 """
 
 from dataclasses import dataclass
+from functools import lru_cache
+
+import numpy as np
 
 _DPM = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)
 
@@ -86,3 +89,61 @@ def monthly_midpoints(start_year, nyears, calendar):
             out.append(_from_day_of_year(y, doy + n / 2.0, calendar))
             doy += n
     return out
+
+
+def daily_midpoints(start_year, nyears, calendar):
+    """Daily ('D') mid-day axis of test_data/time.py:75-94: one step per day of ``nyears`` whole
+    years, each at 12:00."""
+    out = []
+    for y in range(start_year, start_year + nyears):
+        for m in range(1, 13):
+            for d in range(1, days_in_month(y, m, calendar) + 1):
+                out.append(DatetimeLite(y, m, d, 12, 0, calendar))
+    return out
+
+
+@lru_cache(maxsize=None)
+def _year_start_day(year, calendar):
+    """whole days from 1970-01-01 to Jan 1 of ``year``, both in ``calendar``"""
+    if year >= 1970:
+        return sum(days_in_year(y, calendar) for y in range(1970, year))
+    return -sum(days_in_year(y, calendar) for y in range(year, 1970))
+
+
+def day_of_year(t):
+    """1-based day of the year of a calendar object (cftime's ``dayofyr``)"""
+    cal = t.calendar
+    return sum(days_in_month(t.year, m, cal) for m in range(1, t.month)) + t.day
+
+
+def days_since_1970(t):
+    """whole days from 1970-01-01 of the object's own calendar to its date"""
+    return _year_start_day(t.year, t.calendar.lower()) + day_of_year(t) - 1
+
+
+def ns_since_1970(t):
+    """float64 nanoseconds since 1970-01-01 00:00 of the object's own calendar: what xarray's
+    ``get_clean_interp_index`` makes of a CFTimeIndex (datetime_to_numeric, offset 1970-01-01,
+    datetime_unit "ns") -- the x of ``polyfit`` and of ``broadcast_trend``."""
+    seconds = ((days_since_1970(t) * 24 + t.hour) * 60 + t.minute) * 60 + getattr(t, "second", 0)
+    return float(seconds * 1_000_000_000 + getattr(t, "microsecond", 0) * 1000)
+
+
+def is_calendar_axis(values):
+    """does the coordinate hold calendar objects (DatetimeLite, cftime.datetime)?  -- the
+    reference's ``isinstance(index, CFTimeIndex)`` test (trend.py:59-60, :269-270)"""
+    values = np.asarray(values)
+    return (values.dtype == object and values.size > 0
+            and all(hasattr(values.flat[0], a) for a in ("year", "month", "day", "calendar")))
+
+
+def axis_to_numeric(values):
+    """A coordinate as the float64 numbers a fit along it uses: calendar objects -> ns since
+    1970-01-01 00:00 in their calendar; numpy.datetime64 -> ns since the epoch; a numeric
+    coordinate keeps its own values."""
+    values = np.asarray(values)
+    if is_calendar_axis(values):
+        return np.array([ns_since_1970(t) for t in values.ravel()], dtype=np.float64)
+    if values.dtype.kind == "M":
+        return values.astype("datetime64[ns]").astype(np.int64).astype(np.float64)
+    return values.astype(np.float64)

@@ -757,6 +757,134 @@ def group_weighted_mean(x, w, group_len, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# the trend kernels (include/momlevel_trend.h; csrc/momlevel_trend.hip)
+# ---------------------------------------------------------------------------------------
+APPLY_MODES = {
+    "remove": _lib.APPLY_REMOVE, "correct": _lib.APPLY_CORRECT, "trend": _lib.APPLY_TREND,
+    "trend_anom": _lib.APPLY_TREND_ANOM, "model_resid": _lib.APPLY_MODEL_RESID,
+    "model": _lib.APPLY_MODEL,
+}
+
+
+def _time_record(y):
+    """A (time, ...) device record as the kernels read it: C-contiguous, float32 kept (widened in
+    registers), anything else float64.  Returns (tensor, nt, cells, dtype code)."""
+    if not (isinstance(y, torch.Tensor) and y.is_cuda):
+        raise TypeError("the record must be a device tensor")
+    if y.dim() < 1 or y.shape[0] < 1:
+        raise ValueError("the record needs a leading time axis")
+    if y.dtype not in (torch.float32, torch.float64):
+        y = y.to(torch.float64)
+    y = y.contiguous()
+    return y, y.shape[0], y[0].numel(), (DTYPE_F64 if y.dtype == torch.float64 else DTYPE_F32)
+
+
+def _fit_workspace(lib, nt, n, nterms, device):
+    nbytes = lib.mlx_time_fit_workspace_bytes(nt, n, nterms)
+    if n > 0 and nbytes == 0:
+        raise ValueError(f"a record of {nt} steps x {n} cells is outside the fit kernels' range")
+    return torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=device), nbytes
+
+
+def time_linfit(y, xt, s, xmean):
+    """NaN-skipping straight-line fit per cell along the leading axis (mlx_time_linfit): y (nt, ...)
+    float32 / float64, xt (nt,) = (x - xmean) / s  ->  (slope, intercept), float64, shaped
+    y.shape[1:].  Cells with fewer than 2 valid steps give NaN."""
+    require_device()
+    lib = _lib.load_trend()
+    y, nt, n, code = _time_record(y)
+    xt = _f64(xt, y.device).reshape(-1)
+    if xt.numel() != nt:
+        raise ValueError("one xt per time step")
+    slope = torch.empty(y.shape[1:], dtype=torch.float64, device=y.device)
+    intercept = torch.empty_like(slope)
+    if n == 0:
+        return slope, intercept
+    ws, nbytes = _fit_workspace(lib, nt, n, 5, y.device)
+    with _on(y.device):
+        rc = lib.mlx_time_linfit(_ptr(y), code, _ptr(xt), nt, n, float(s), float(xmean),
+                                 _ptr(slope), _ptr(intercept), _ptr(ws), nbytes, _stream(y.device))
+    _lib.check(rc, "mlx_time_linfit")
+    return slope, intercept
+
+
+def time_project(y, P):
+    """coef[k] = sum_t P[t, k] * y[t] per cell (mlx_time_project): y (nt, ...), P (nt, K) with
+    K <= 8  ->  (K, ...) float64.  NaN propagates: one NaN step makes the cell's K values NaN."""
+    require_device()
+    lib = _lib.load_trend()
+    y, nt, n, code = _time_record(y)
+    P = _f64(P, y.device)
+    if P.dim() != 2 or P.shape[0] != nt or not 1 <= P.shape[1] <= _lib.TREND_MAX_TERMS:
+        raise ValueError(f"P must be (nt, K) with 1 <= K <= {_lib.TREND_MAX_TERMS}")
+    K = P.shape[1]
+    coef = torch.empty((K,) + tuple(y.shape[1:]), dtype=torch.float64, device=y.device)
+    if n == 0:
+        return coef
+    ws, nbytes = _fit_workspace(lib, nt, n, K, y.device)
+    with _on(y.device):
+        rc = lib.mlx_time_project(_ptr(y), code, _ptr(P), K, nt, n, _ptr(coef), _ptr(ws), nbytes,
+                                  _stream(y.device))
+    _lib.check(rc, "mlx_time_project")
+    return coef
+
+
+def time_apply(y, mode, xm, a, b=None, out=None):
+    """The elementwise pass (mlx_time_apply).  Straight-line modes "remove" / "correct" /
+    "trend" / "trend_anom": xm = x (nt,), a = slope, b = intercept ("remove").  Model modes
+    "model_resid" / "model": xm = M (K, nt), a = coef (K, ...).  ``y`` (nt, ...) may be None in the
+    modes that do not read it.  Returns (nt, ...) float64."""
+    require_device()
+    lib = _lib.load_trend()
+    code_mode = APPLY_MODES[mode]
+    model = mode in ("model_resid", "model")
+    reads_y = mode in ("remove", "correct", "model_resid")
+    a = _f64(a, a.device)
+    device = a.device
+    xm = _f64(xm, device)
+    if model and (xm.dim() != 2 or a.dim() < 1 or a.shape[0] != xm.shape[0]):
+        raise ValueError("model modes take M (K, nt) and coef (K, ...)")
+    K = xm.shape[0] if model else 0
+    nt = xm.shape[1] if model else xm.numel()
+    cells_shape = tuple(a.shape[1:]) if model else tuple(a.shape)
+    n = int(np.prod(cells_shape, dtype=np.int64))
+    code = DTYPE_F64
+    if reads_y:
+        y, ynt, yn, code = _time_record(y)
+        if ynt != nt or tuple(y.shape[1:]) != cells_shape:
+            raise ValueError("y must be (nt,) + the cells' shape")
+    else:
+        y = None
+    if mode == "remove":
+        if b is None:
+            raise ValueError('mode "remove" needs the intercept')
+        b = _f64(b, device)
+        if tuple(b.shape) != cells_shape:
+            raise ValueError("slope and intercept must agree in shape")
+    else:
+        b = None
+    if out is None:
+        out = torch.empty((nt,) + cells_shape, dtype=torch.float64, device=device)
+    if n == 0:
+        return out
+    step = 65535 * 64  # the kernel's grid.y carries the time axis in windows of 64 steps
+    for t0 in range(0, nt, step):
+        t1 = min(t0 + step, nt)
+        if model:
+            xs = xm[:, t0:t1].contiguous() if (t0, t1) != (0, nt) else xm
+        else:
+            xs = xm[t0:t1]
+            if mode == "trend_anom" and t0:
+                raise ValueError("trend_anom: time axis too long for one call")
+        with _on(device):
+            rc = lib.mlx_time_apply(_ptr(y[t0:t1]) if reads_y else None, code, code_mode, _ptr(xs),
+                                    _ptr(a), _ptr(b), K, t1 - t0, n, _ptr(out[t0:t1]),
+                                    _stream(device))
+        _lib.check(rc, "mlx_time_apply")
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

@@ -17,12 +17,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
-           os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "host_copy.cpp")]
+           os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
+           os.path.join(HERE, "host_copy.cpp")]
 DEPENDS = SOURCES + [
     os.path.join(HERE, "eos_device.hpp"),
     os.path.join(HERE, "eos_promote.hpp"),
     os.path.join(HERE, "mlx_internal.hpp"),
     os.path.join(ROOT, "include", "momlevel_hip.h"),
+    os.path.join(ROOT, "include", "momlevel_trend.h"),
     os.path.abspath(__file__),
 ]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
@@ -71,6 +73,13 @@ def strat_source_sha():
     """the stratification kernels' own guard: csrc/momlevel_strat.hip (+ what it includes, + flags)"""
     return source_sha([os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "eos_device.hpp"),
                        os.path.join(HERE, "mlx_internal.hpp")])
+
+
+def trend_source_sha():
+    """the trend kernels' own guard: csrc/momlevel_trend.hip (+ what it includes, + flags)"""
+    return source_sha([os.path.join(HERE, "momlevel_trend.hip"), os.path.join(HERE, "eos_device.hpp"),
+                       os.path.join(HERE, "mlx_internal.hpp"),
+                       os.path.join(ROOT, "include", "momlevel_trend.h")])
 
 
 def hipcc():

@@ -18,6 +18,7 @@ __all__ = [
     "annual_average",
     "default_coords",
     "eos_func_from_str",
+    "linear_detrend",
     "validate_areacello",
     "validate_dataset",
 ]
@@ -236,3 +237,16 @@ def annual_average(xobj, tcoord="time"):
             result[name] = avg(var)
         return result
     return avg(xobj)
+
+
+def linear_detrend(*args, **kwargs):
+    """Deprecated shim of util.py:863-870: use ``momlevel_amd.trend.linear_detrend``."""
+    from . import trend
+
+    warnings.warn(
+        "`util.linear_trend()` will be removed. "
+        + "Please use version in the new `momlevel.trend` module",
+        DeprecationWarning,
+        stacklevel=2,
+    )
+    return trend.linear_detrend(*args, **kwargs)

@@ -3,7 +3,7 @@
 
     python scripts/sanitize_host.py [--iters N] [--keep]
 
-1. compiles momlevel_amd/csrc/momlevel_hip.hip, momlevel_promote.hip and host_copy.cpp with the HOST pass instrumented by
+1. compiles the library's sources (momlevel_amd.csrc.build.SOURCES) with the HOST pass instrumented by
    AddressSanitizer + UndefinedBehaviorSanitizer (``-fsanitize=address,undefined
    -fno-gpu-sanitize``: the gfx950 device code is built as always and never instrumented -- GPU
    ASan is not available on this pool and is not used) into build/sanitize/libmomlevel_hip.so;
@@ -41,12 +41,11 @@ def main():
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     lib = os.path.join(OUT, "libmomlevel_hip.so")
-    csrc = os.path.join(ROOT, "momlevel_amd", "csrc")
-    srcs = [os.path.join(csrc, "momlevel_hip.hip"), os.path.join(csrc, "momlevel_promote.hip"),
-            os.path.join(csrc, "momlevel_strat.hip"), os.path.join(csrc, "host_copy.cpp")]
-    deps = srcs + [os.path.join(csrc, "eos_device.hpp"), os.path.join(csrc, "eos_promote.hpp"),
-                   os.path.join(csrc, "mlx_internal.hpp"),
-                   os.path.join(ROOT, "include", "momlevel_hip.h"), os.path.abspath(__file__)]
+    sys.path.insert(0, ROOT)
+    from momlevel_amd.csrc import build  # the library's own source list: nothing to keep in step
+
+    srcs = list(build.SOURCES)
+    deps = list(build.DEPENDS) + [os.path.abspath(__file__)]
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(map(os.path.getmtime, deps)):
         run([hipcc(), "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
              "-std=c++17"] + SAN + srcs + ["-o", lib], check=True)
