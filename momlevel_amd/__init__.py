@@ -2,9 +2,10 @@
 
 A drop-in for one path of jkrasting/momlevel: the Wright (1997) in-situ density and
 the volume-weighted reductions behind ``steric`` / ``halosteric`` / ``thermosteric``
-and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, and the per-cell trend,
-detrend and deseason fits of ``trend``, computed by hand-written HIP kernels behind a
-C ABI (include/momlevel_hip.h, include/momlevel_trend.h).  Everything else in momlevel
+and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, the per-cell trend,
+detrend and deseason fits of ``trend``, and the grouped time statistics
+``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
+C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h).  Everything else in momlevel
 (tide gauges, vorticity, spiciness, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute

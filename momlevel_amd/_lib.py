@@ -35,6 +35,8 @@ STRAT_N2, STRAT_TURNER = 0, 1  # mlx_stratification's func
 TREND_MAX_TERMS = 8
 (APPLY_REMOVE, APPLY_CORRECT, APPLY_TREND, APPLY_TREND_ANOM, APPLY_MODEL_RESID,
  APPLY_MODEL) = range(6)
+# ---- constants mirrored from include/momlevel_clim.h -------------------------------
+STAT_MEAN, STAT_STD, STAT_MIN, STAT_MAX = range(4)
 
 
 def flag_tchunk(steps):
@@ -133,6 +135,13 @@ TREND_SIGNATURES = {
 }
 
 
+# The grouped time statistic (include/momlevel_clim.h): bound by load_clim() on first use, for the
+# same reason.
+CLIM_SIGNATURES = {
+    "mlx_clim_group_stat": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -199,6 +208,29 @@ def load_trend():
         fn.restype = restype
         fn.argtypes = argtypes
     _trend_bound = True
+    return lib
+
+
+_clim_bound = False
+
+
+def load_clim():
+    """load(), then declare the prototypes of include/momlevel_clim.h (once); a library built
+    without csrc/momlevel_clim.hip raises ``MomlevelHipError``."""
+    global _clim_bound
+    lib = load()
+    if _clim_bound:
+        return lib
+    for name, (restype, argtypes) in CLIM_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise MomlevelHipError(
+                f"{LIB_PATH} does not export {name}: rebuild it with the grouped-statistic kernel "
+                "(`python -m momlevel_amd.csrc.build --force`)") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _clim_bound = True
     return lib
 
 

@@ -885,6 +885,84 @@ def time_apply(y, mode, xm, a, b=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# the grouped time statistic (include/momlevel_clim.h; csrc/momlevel_clim.hip)
+# ---------------------------------------------------------------------------------------
+STAT_IDS = {"mean": _lib.STAT_MEAN, "std": _lib.STAT_STD, "min": _lib.STAT_MIN,
+            "max": _lib.STAT_MAX}
+
+
+def check_groups(steps, offsets, nt):
+    """The host-side mirror of a group list as the kernel reads it: ``(steps int32 (nsel),
+    offsets int64 (ngroups + 1))``, or ``ValueError`` -- a step outside [0, nt), offsets that
+    decrease or leave [0, nsel], no group or no step at all.  Touches no device."""
+    steps = np.ascontiguousarray(np.asarray(steps).reshape(-1))
+    offsets = np.ascontiguousarray(np.asarray(offsets).reshape(-1))
+    if steps.dtype.kind not in "iu" or offsets.dtype.kind not in "iu":
+        raise ValueError("steps and offsets must hold integers")
+    if steps.size < 1 or offsets.size < 2:
+        raise ValueError("need at least one step and one group (offsets holds ngroups + 1 values)")
+    if int(steps.min()) < 0 or int(steps.max()) >= int(nt):
+        raise ValueError(f"steps must lie in [0, {int(nt)})")
+    if int(offsets[0]) < 0 or int(offsets[-1]) > steps.size or np.any(np.diff(offsets.astype(np.int64)) < 0):
+        raise ValueError(f"offsets must not decrease and must lie in [0, {steps.size}]")
+    return steps.astype(np.int32), offsets.astype(np.int64)
+
+
+class DeviceGroups:
+    """A checked group list on the device: what ``time_group_stat`` takes in place of host
+    ``steps`` / ``offsets`` when the same groups serve several calls."""
+
+    def __init__(self, steps, offsets, nt, device):
+        steps, offsets = check_groups(steps, offsets, nt)
+        self.nt, self.nsel, self.ngroups = int(nt), int(steps.size), int(offsets.size - 1)
+        # (integer lists: a plain copy -- hostio's staging carries floating fields only)
+        self.steps = torch.from_numpy(steps).to(device)
+        self.offsets = torch.from_numpy(offsets).to(device)
+
+
+def upload_groups(steps, offsets, nt, device):
+    """``check_groups``, then the two lists on ``device`` (a ``DeviceGroups``)."""
+    return DeviceGroups(steps, offsets, nt, torch.device(device))
+
+
+def time_group_stat(y, steps, offsets=None, stat="mean", out=None):
+    """NaN-skipping ``stat`` ("mean", "std", "min", "max") over groups of steps of the leading
+    axis (mlx_clim_group_stat): y (nt, ...) float32 / float64 on the device; group g is
+    ``steps[offsets[g]:offsets[g + 1]]``, visited in that order  ->  (ngroups, ...) of y's dtype.
+    ``steps`` / ``offsets`` are host integer sequences, checked here before they are uploaded, or
+    ``steps`` is a ``DeviceGroups`` made by ``upload_groups`` (``offsets`` None).  float64 results
+    are bit-identical to numpy's nanmean / nanstd / nanmin / nanmax over axis 0 of ``y[sel]``;
+    float32 records are accumulated in float64 and rounded once."""
+    require_device()
+    lib = _lib.load_clim()
+    if stat not in STAT_IDS:
+        raise ValueError(f"stat must be one of {sorted(STAT_IDS)}, got '{stat}'")
+    y, nt, n, code = _time_record(y)
+    if isinstance(steps, DeviceGroups):
+        groups = steps
+        if offsets is not None:
+            raise ValueError("a DeviceGroups carries its own offsets")
+        if groups.nt != nt or groups.steps.device != y.device:
+            raise ValueError("the groups were made for another record length or device")
+    else:
+        groups = DeviceGroups(steps, offsets, nt, y.device)
+    shape = (groups.ngroups,) + tuple(y.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=y.dtype, device=y.device)
+    elif (tuple(out.shape) != shape or out.dtype != y.dtype or out.device != y.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {y.dtype} tensor of shape {shape} on {y.device}")
+    if n == 0:
+        return out
+    with _on(y.device):
+        rc = lib.mlx_clim_group_stat(_ptr(y), code, _ptr(groups.steps), _ptr(groups.offsets),
+                                     groups.nsel, groups.ngroups, nt, n, STAT_IDS[stat], _ptr(out),
+                                     _stream(y.device))
+    _lib.check(rc, "mlx_clim_group_stat")
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

@@ -18,13 +18,14 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
            os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
-           os.path.join(HERE, "host_copy.cpp")]
+           os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "host_copy.cpp")]
 DEPENDS = SOURCES + [
     os.path.join(HERE, "eos_device.hpp"),
     os.path.join(HERE, "eos_promote.hpp"),
     os.path.join(HERE, "mlx_internal.hpp"),
     os.path.join(ROOT, "include", "momlevel_hip.h"),
     os.path.join(ROOT, "include", "momlevel_trend.h"),
+    os.path.join(ROOT, "include", "momlevel_clim.h"),
     os.path.abspath(__file__),
 ]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
@@ -80,6 +81,13 @@ def trend_source_sha():
     return source_sha([os.path.join(HERE, "momlevel_trend.hip"), os.path.join(HERE, "eos_device.hpp"),
                        os.path.join(HERE, "mlx_internal.hpp"),
                        os.path.join(ROOT, "include", "momlevel_trend.h")])
+
+
+def clim_source_sha():
+    """the grouped-statistic kernel's own guard: csrc/momlevel_clim.hip (+ what it includes, + flags)"""
+    return source_sha([os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "eos_device.hpp"),
+                       os.path.join(HERE, "mlx_internal.hpp"),
+                       os.path.join(ROOT, "include", "momlevel_clim.h")])
 
 
 def hipcc():

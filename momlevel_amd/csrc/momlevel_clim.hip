@@ -1,0 +1,292 @@
+// momlevel_clim.hip -- a NaN-skipping statistic over groups of time steps of a (time, cells)
+// record, one result row per group (include/momlevel_clim.h):
+//
+//   util.monthly_average  (src/momlevel/util.py:454-511)   groupby year, groupby month, .mean
+//   util.annual_cycle     (src/momlevel/util.py:122-196)   groupby month, .mean/.std/.min/.max
+//
+// The reference does these through xarray's groupby on one CPU thread.  Here a group is a list of
+// time indices (steps[offsets[g] .. offsets[g + 1])): calendar months of a daily record have 28 to
+// 31 steps, the steps of "all Januaries" lie 12 rows apart.  A lane owns a pack of horizontally
+// adjacent cells (16-byte nontemporal loads: two float64 or four float32) and walks ONE group in
+// the order steps[] lists it, with kClimUnroll row loads in flight ahead of the dependent adds:
+// the add chain is sequential by contract (bit-identical to numpy's nanmean / nanstd over axis 0).
+// The step indices are wave-uniform and come through the scalar cache, one batch ahead of the
+// rows they address.  MEAN, MIN and MAX read every selected element once (8 B, 4 B at float32,
+// per cell-step); STD reads the group twice (mean, then squared deviations), as numpy does.
+//
+// grid = (cell tiles, min(ngroups, 65535)); a block loops over g = blockIdx.y, += gridDim.y, so
+// any number of groups works (a daily record with one group per step has more than 65535).  No
+// group is ever split between threads and there are no atomics: results do not depend on the
+// launch geometry or on how a caller blocks the cells.
+//
+// Cells that do not fill a pack (n not a multiple of it, or rows that are then not 16-byte
+// aligned) are handled by the narrower instantiations, down to one cell per lane.
+//
+// Compile: with momlevel_hip.hip (csrc/build.py), -ffp-contract=off -- STD's d * d and the add
+// that follows must stay two operations.  Not part of the kernel sources whose hash guards the
+// committed steric profiles (build.clim_source_sha is this file's).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/momlevel_hip.h"
+#include "../../include/momlevel_clim.h"
+#include "eos_device.hpp"
+#include "mlx_internal.hpp"
+
+#pragma clang fp contract(off)
+
+namespace mlx {
+namespace {
+
+constexpr int kClimBlock = 256;  // 4 waves of 64
+constexpr int kClimUnroll = 8;   // row packs a lane has in flight
+constexpr unsigned kClimMaxGridY = 65535;
+
+typedef float cf4_t __attribute__((ext_vector_type(4)));
+typedef float cf2_t __attribute__((ext_vector_type(2)));
+
+template <typename T, int V>
+struct CPack {
+  T v[V];
+};
+
+// once-read data moves with the `nt` cache policy (the idiom of momlevel_hip.hip's load_pack):
+// one global_load_dword / dwordx2 / dwordx4 per lane
+template <typename TIn, int V>
+__device__ __forceinline__ CPack<TIn, V> cl_load(const TIn* __restrict__ p) {
+  CPack<TIn, V> r;
+  if constexpr (V == 1) {
+    r.v[0] = __builtin_nontemporal_load(p);
+  } else if constexpr (sizeof(TIn) == 4 && V == 2) {
+    cf2_t raw = __builtin_nontemporal_load(reinterpret_cast<const cf2_t*>(p));
+    r.v[0] = raw.x;
+    r.v[1] = raw.y;
+  } else {
+    static_assert(sizeof(TIn) * V == 16, "a pack is at most 16 bytes");
+    cf4_t raw = __builtin_nontemporal_load(reinterpret_cast<const cf4_t*>(p));
+    __builtin_memcpy(&r, &raw, 16);
+  }
+  return r;
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void cl_store(T* __restrict__ p, const CPack<T, V>& r) {
+  if constexpr (V == 1) {
+    p[0] = r.v[0];
+  } else if constexpr (sizeof(T) == 4 && V == 2) {
+    cf2_t raw = {r.v[0], r.v[1]};
+    *reinterpret_cast<cf2_t*>(p) = raw;
+  } else {
+    static_assert(sizeof(T) * V == 16, "a pack is at most 16 bytes");
+    cf4_t raw;
+    __builtin_memcpy(&raw, &r, 16);
+    *reinterpret_cast<cf4_t*>(p) = raw;
+  }
+}
+
+// The row of step index s, widened to float64.  s is wave-uniform.  An index outside [0, nt) --
+// a caller's mistake the entry point cannot see -- reads row 0 and yields NaN: never out of bounds.
+template <typename TIn, int V>
+struct Row {
+  CPack<TIn, V> raw;
+  bool ok;
+  __device__ __forceinline__ double at(int k) const {
+    return ok ? (double)raw.v[k] : canonical_nan();  // float32 -> float64 is exact
+  }
+};
+
+template <typename TIn, int V>
+__device__ __forceinline__ Row<TIn, V> row_load(const TIn* __restrict__ ycol, int32_t s, int64_t nt,
+                                                int64_t n) {
+  Row<TIn, V> r;
+  r.ok = (uint32_t)s < (uint32_t)nt;
+  r.raw = cl_load<TIn, V>(ycol + (int64_t)(r.ok ? s : 0) * n);
+  return r;
+}
+
+// Visit the rows steps[lo .. hi) in order: kClimUnroll loads are issued before the first of them
+// is consumed, and the next batch of step indices is fetched before the loads of this one.
+template <typename TIn, int V, typename F>
+__device__ __forceinline__ void walk_group(const TIn* __restrict__ ycol,
+                                           const int32_t* __restrict__ steps, int64_t lo, int64_t hi,
+                                           int64_t nt, int64_t n, F&& consume) {
+  constexpr int U = kClimUnroll;
+  int64_t j = lo;
+  if (j + U <= hi) {
+    int32_t cur[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = steps[j + u];
+    for (; j + U <= hi; j += U) {
+      int32_t nxt[U];
+      const int64_t ahead = j + 2 * U <= hi ? j + U : j;  // (the last batch re-reads itself)
+#pragma unroll
+      for (int u = 0; u < U; ++u) nxt[u] = steps[ahead + u];
+      Row<TIn, V> r[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) r[u] = row_load<TIn, V>(ycol, cur[u], nt, n);
+#pragma unroll
+      for (int u = 0; u < U; ++u) consume(r[u]);
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+  }
+  for (; j < hi; ++j) consume(row_load<TIn, V>(ycol, steps[j], nt, n));
+}
+
+// ------------------------------------------------------------------------------------------
+// k_group_stat: out[g][cell] = STAT over the steps of group g.  n % V == 0.
+// ------------------------------------------------------------------------------------------
+template <typename TIn, int V, int STAT>
+__global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict__ y,
+                                                           const int32_t* __restrict__ steps,
+                                                           const int64_t* __restrict__ offsets,
+                                                           int64_t nsel, int64_t ngroups, int64_t nt,
+                                                           int64_t n, TIn* __restrict__ out) {
+  const int64_t i = ((int64_t)blockIdx.x * kClimBlock + threadIdx.x) * V;
+  if (i >= n) return;
+  const TIn* ycol = y + i;
+  for (int64_t g = blockIdx.y; g < ngroups; g += gridDim.y) {
+    int64_t lo = offsets[g], hi = offsets[g + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > nsel ? nsel : hi;
+    double res[V];
+    if constexpr (STAT == MLX_STAT_MEAN || STAT == MLX_STAT_STD) {
+      // -0.0 + x is x for every x, and -0.0 + (+0.0) is +0.0: the sum starts as the first step's
+      // value, or as +0.0 when that is NaN -- numpy's sum over the NaN-zeroed rows
+      double acc[V], cnt[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        acc[k] = -0.0;
+        cnt[k] = 0.0;
+      }
+      walk_group<TIn, V>(ycol, steps, lo, hi, nt, n, [&](const Row<TIn, V>& r) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          const double yv = r.at(k);
+          const bool bad = is_nan(yv);
+          acc[k] += bad ? 0.0 : yv;
+          cnt[k] += bad ? 0.0 : 1.0;
+        }
+      });
+#pragma unroll
+      for (int k = 0; k < V; ++k) res[k] = cnt[k] == 0.0 ? canonical_nan() : acc[k] / cnt[k];
+      if constexpr (STAT == MLX_STAT_STD) {
+        double ss[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) ss[k] = 0.0;
+        walk_group<TIn, V>(ycol, steps, lo, hi, nt, n, [&](const Row<TIn, V>& r) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) {
+            const double yv = r.at(k);
+            const double d = yv - res[k];
+            const double sq = d * d;
+            ss[k] += is_nan(yv) ? 0.0 : sq;
+          }
+        });
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+          res[k] = cnt[k] == 0.0 ? canonical_nan() : __dsqrt_rn(ss[k] / cnt[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k) res[k] = canonical_nan();
+      walk_group<TIn, V>(ycol, steps, lo, hi, nt, n, [&](const Row<TIn, V>& r) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          const double yv = r.at(k);
+          const bool better = STAT == MLX_STAT_MIN ? yv < res[k] : yv > res[k];  // false for NaN yv
+          res[k] = (better || (is_nan(res[k]) && !is_nan(yv))) ? yv : res[k];
+        }
+      });
+    }
+    CPack<TIn, V> o;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if constexpr (sizeof(TIn) == 8) {
+        o.v[k] = is_nan(res[k]) ? canonical_nan() : res[k];
+      } else {
+        o.v[k] = is_nan(res[k]) ? canonical_nan_f32() : (float)res[k];  // the one rounding
+      }
+    }
+    cl_store<TIn, V>(out + g * n + i, o);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+using detail::fail;
+using detail::hip_status;
+
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b != 0); }
+
+constexpr int64_t kMaxCells = (int64_t)1 << 38;
+constexpr int64_t kMaxSteps = (int64_t)1 << 31;
+
+template <typename TIn, int V, int STAT>
+int launch_stat(const void* y, const int32_t* steps, const int64_t* offsets, int64_t nsel,
+                int64_t ngroups, int64_t nt, int64_t n, void* out, hipStream_t st) {
+  const unsigned gy = ngroups < (int64_t)kClimMaxGridY ? (unsigned)ngroups : kClimMaxGridY;
+  dim3 grid((unsigned)ceil_div(n, (int64_t)kClimBlock * V), gy);
+  hipLaunchKernelGGL((k_group_stat<TIn, V, STAT>), grid, dim3(kClimBlock), 0, st, (const TIn*)y,
+                     steps, offsets, nsel, ngroups, nt, n, (TIn*)out);
+  return hip_status(hipGetLastError(), "k_group_stat launch");
+}
+
+template <typename TIn, int V>
+int launch_any(int stat, const void* y, const int32_t* steps, const int64_t* offsets, int64_t nsel,
+               int64_t ngroups, int64_t nt, int64_t n, void* out, hipStream_t st) {
+  switch (stat) {
+    case MLX_STAT_MEAN:
+      return launch_stat<TIn, V, MLX_STAT_MEAN>(y, steps, offsets, nsel, ngroups, nt, n, out, st);
+    case MLX_STAT_STD:
+      return launch_stat<TIn, V, MLX_STAT_STD>(y, steps, offsets, nsel, ngroups, nt, n, out, st);
+    case MLX_STAT_MIN:
+      return launch_stat<TIn, V, MLX_STAT_MIN>(y, steps, offsets, nsel, ngroups, nt, n, out, st);
+    default:
+      return launch_stat<TIn, V, MLX_STAT_MAX>(y, steps, offsets, nsel, ngroups, nt, n, out, st);
+  }
+}
+
+}  // namespace
+}  // namespace mlx
+
+using namespace mlx;
+
+extern "C" {
+
+int mlx_clim_group_stat(const void* y, int dtype, const int32_t* steps, const int64_t* offsets,
+                        int64_t nsel, int64_t ngroups, int64_t nt, int64_t n, int stat, void* out,
+                        void* stream) {
+  if (!y || !steps || !offsets || !out)
+    return fail(MLX_E_NULL, "y, steps, offsets, out must not be NULL");
+  if (dtype != MLX_DTYPE_F64 && dtype != MLX_DTYPE_F32)
+    return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
+  if (stat < MLX_STAT_MEAN || stat > MLX_STAT_MAX) return fail(MLX_E_ENUM, "unknown MLX_STAT_* stat");
+  int64_t total, rows;
+  if (nt <= 0 || n <= 0 || nsel <= 0 || ngroups <= 0 || nt >= kMaxSteps || nsel >= kMaxSteps ||
+      n > kMaxCells || __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
+      __builtin_mul_overflow(ngroups, n, &rows) || rows > INT64_MAX / 64 ||
+      ceil_div(n, kClimBlock) > 2147483647LL)
+    return fail(MLX_E_SHAPE,
+                "need 0 < nt, nsel < 2^31, ngroups > 0, 0 < n <= 2^38, nt*n and ngroups*n addressable");
+  const size_t elem = dtype == MLX_DTYPE_F64 ? 8 : 4;
+  if (!aligned(y, elem) || !aligned(out, elem)) return fail(MLX_E_ALIGN, "y / out not element-aligned");
+  if (!aligned(steps, 4) || !aligned(offsets, 8))
+    return fail(MLX_E_ALIGN, "steps not 4-byte or offsets not 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  // cells per lane: the widest pack (16 bytes at most) that divides every row and keeps every row
+  // of the record and of the result pack-aligned
+  int v = (int)(16 / elem);
+  while (v > 1 && (n % v || !aligned(y, elem * v) || !aligned(out, elem * v))) v /= 2;
+  if (dtype == MLX_DTYPE_F64)
+    return v == 2 ? launch_any<double, 2>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
+                  : launch_any<double, 1>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st);
+  return v == 4   ? launch_any<float, 4>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
+         : v == 2 ? launch_any<float, 2>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
+                  : launch_any<float, 1>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st);
+}
+
+}  // extern "C"

@@ -184,7 +184,8 @@ class _Record:
             c1 = min(c0 + block, self.n)
             res = fn(hostio.to_device(self.y[:, c0:c1], device))
             if outs is None:
-                outs = [np.empty(tuple(r.shape[:-1]) + (self.n,), dtype=np.float64) for r in res]
+                outs = [np.empty(tuple(r.shape[:-1]) + (self.n,), dtype=np_dtype(r.dtype))
+                        for r in res]  # (float64 for every fit; a grouped statistic keeps float32)
             for o, r in zip(outs, res):
                 o[..., c0:c1] = hostio.to_host(r)
         if outs is None:  # no cells at all

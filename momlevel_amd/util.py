@@ -12,13 +12,16 @@ import warnings
 import numpy as np
 
 from . import eos
+from .adapters import accepts_xarray
 from .labeled import DataArray, Dataset
 
 __all__ = [
     "annual_average",
+    "annual_cycle",
     "default_coords",
     "eos_func_from_str",
     "linear_detrend",
+    "monthly_average",
     "validate_areacello",
     "validate_dataset",
 ]
@@ -237,6 +240,48 @@ def annual_average(xobj, tcoord="time"):
             result[name] = avg(var)
         return result
     return avg(xobj)
+
+
+@accepts_xarray
+def monthly_average(xobj, tcoord="time"):
+    """Monthly means of daily (or any sub-monthly) data (util.py:454-511): one step per calendar
+    month of every year present, the new time axis holding the months' mid-points; the result has
+    ``tcoord`` leading.  It is what makes a daily record acceptable to ``annual_cycle`` and
+    ``annual_average``.
+
+    Accepts a labelled Dataset or DataArray (xarray objects through the adapter) whose time
+    coordinate holds calendar objects.  One HIP pass (mlx_clim_group_stat) averages every month of
+    every cell, NaNs skipped: float64 results are bit-identical to numpy's nanmean over the month's
+    rows; float32 keeps its dtype (accumulated in float64, rounded once); integers and booleans give
+    float64; float16 / long double are refused.  Device data stays on the device.  Dataset:
+    non-numeric variables are skipped, variables without ``tcoord`` are left out, coordinates not
+    on ``tcoord`` and the variables' attrs and encoding are kept.  A year that lacks a calendar
+    month is a ``ValueError``.  Parity with real xarray objects is unpinned: xarray is not
+    importable where the tests run."""
+    from . import climatology
+
+    return climatology.grouped_stat(xobj, tcoord, climatology.monthly_plan(xobj[tcoord], tcoord),
+                                    "mean")
+
+
+@accepts_xarray
+def annual_cycle(xobj, tcoord="time", func="mean", time_axis_year=None):
+    """Annual-cycle climatology of a monthly record (util.py:122-196): ``func`` ("mean", "std",
+    "min" or "max") over all steps of each calendar month -- 12 time points, the month mid-points
+    of ``time_axis_year`` or, without it, of the year in the middle of the record.  An unknown
+    ``func`` is a ``ValueError``, as is a record that lacks a calendar month.
+
+    One HIP pass (mlx_clim_group_stat; two reads of the record for "std") over every cell, NaNs
+    skipped: float64 results are bit-identical to numpy's nanmean / nanstd (ddof = 0) / nanmin /
+    nanmax.  Dtypes, placement and Dataset handling as ``monthly_average``; integer records give
+    float64 for every ``func`` (xarray keeps integers for min / max).  Parity with real xarray
+    objects is unpinned: xarray is not importable where the tests run."""
+    from . import climatology
+
+    if func not in climatology.STATS:
+        raise ValueError(f"Unknown argument 'func={func}' to annual cycle")
+    plan = climatology.annual_cycle_plan(xobj[tcoord], tcoord, time_axis_year)
+    return climatology.grouped_stat(xobj, tcoord, plan, func)
 
 
 def linear_detrend(*args, **kwargs):
