@@ -5,8 +5,16 @@ the volume-weighted reductions behind ``steric`` / ``halosteric`` / ``thermoster
 and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, the per-cell trend,
 detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
-C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h).  Everything else in momlevel
-(tide gauges, vorticity, spiciness, ...) is out of scope -- use momlevel.
+C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
+include/momlevel_gauge.h).
+
+``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
+wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
+the lowest flat index) and the gauges' series, gathered in one launch -- a device-resident record
+reaches its gauges without a download.  ``util.geolocate_points`` is the same search on pandas
+frames.  The reference's gauge tables are not shipped: pass a CSV path or an in-memory table.
+
+Everything else in momlevel (vorticity, spiciness, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
 entry points raise ``MomlevelHipError``.
@@ -19,6 +27,7 @@ from . import dynamic
 from . import eos
 from . import reference
 from . import test_data
+from . import tidegauge
 from . import timeseries_data
 from . import trend
 from . import util
@@ -45,6 +54,7 @@ __all__ = [
     "steric_variants",
     "test_data",
     "thermosteric",
+    "tidegauge",
     "trend",
     "util",
 ]

@@ -37,6 +37,9 @@ TREND_MAX_TERMS = 8
  APPLY_MODEL) = range(6)
 # ---- constants mirrored from include/momlevel_clim.h -------------------------------
 STAT_MEAN, STAT_STD, STAT_MIN, STAT_MAX = range(4)
+# ---- constants mirrored from include/momlevel_gauge.h ------------------------------
+GAUGE_ROW_X, GAUGE_ROW_Y, GAUGE_ROW_Z, GAUGE_ROW_PHI, GAUGE_ROW_LAM = range(5)
+GAUGE_ROWS = 5
 
 
 def flag_tchunk(steps):
@@ -142,6 +145,17 @@ CLIM_SIGNATURES = {
 }
 
 
+# The tide-gauge entry points (include/momlevel_gauge.h): bound by load_gauge() on first use, for
+# the same reason.
+GAUGE_SIGNATURES = {
+    "mlx_gauge_prepare": (_int, [_vp, _vp, _int, _vp, _int, _i64, _vp, _vp, _vp]),
+    "mlx_gauge_nearest_split": (_i64, [_i64, _i64, _i64]),
+    "mlx_gauge_nearest_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mlx_gauge_nearest": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "mlx_gauge_gather": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -231,6 +245,29 @@ def load_clim():
         fn.restype = restype
         fn.argtypes = argtypes
     _clim_bound = True
+    return lib
+
+
+_gauge_bound = False
+
+
+def load_gauge():
+    """load(), then declare the prototypes of include/momlevel_gauge.h (once); a library built
+    without csrc/momlevel_gauge.hip raises ``MomlevelHipError``."""
+    global _gauge_bound
+    lib = load()
+    if _gauge_bound:
+        return lib
+    for name, (restype, argtypes) in GAUGE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise MomlevelHipError(
+                f"{LIB_PATH} does not export {name}: rebuild it with the tide-gauge kernels "
+                "(`python -m momlevel_amd.csrc.build --force`)") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _gauge_bound = True
     return lib
 
 

@@ -963,6 +963,140 @@ def time_group_stat(y, steps, offsets=None, stat="mean", out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# tide gauges (include/momlevel_gauge.h; csrc/momlevel_gauge.hip)
+# ---------------------------------------------------------------------------------------
+def _gauge_operand(x, device, what):
+    """lat / lon / mask as the prepare kernel reads them: flat, contiguous, on ``device``; float32
+    stays (widened exactly in registers), every other dtype becomes float64."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        return x.to(device).reshape(-1).contiguous()
+    x = np.asarray(x)
+    if x.dtype.kind not in "fiub":
+        raise TypeError(f"{what} must be numeric, got {x.dtype}")
+    dt = torch.float32 if x.dtype == np.float32 else torch.float64
+    x = np.ascontiguousarray(x.reshape(-1), dtype=np.float32 if dt == torch.float32 else np.float64)
+    return hostio.to_device(x, device, dt).contiguous()
+
+
+def gauge_prepare(lat, lon, mask=None, device=None):
+    """Unit vectors, radians and validity of ``n`` positions (mlx_gauge_prepare): lat, lon in
+    degrees, of any shape with ``n`` elements, numpy or device tensors; ``mask`` optional, same
+    element count -- a point is valid iff its mask value == 1.0 exactly (NaN, 0.5: dry) and its
+    coordinates are finite  ->  ``(table (5, n) float64, valid (n) uint8)`` on the device: rows x,
+    y, z (+inf for an invalid point), phi, lam (NaN for one).  Gauges are prepared the same way."""
+    require_device()
+    lib = _lib.load_gauge()
+    if device is None:
+        device = next((x.device for x in (lat, lon, mask)
+                       if isinstance(x, torch.Tensor) and x.is_cuda), torch.device("cuda"))
+    device = torch.device(device)
+    lat = _gauge_operand(lat, device, "lat")
+    lon = _gauge_operand(lon, device, "lon")
+    if lat.numel() != lon.numel():
+        raise ValueError("lat and lon must hold the same number of points")
+    if lat.dtype != lon.dtype:
+        lat, lon = lat.to(torch.float64), lon.to(torch.float64)
+    n = lat.numel()
+    mcode = DTYPE_F64
+    if mask is not None:
+        mask = _gauge_operand(mask, device, "mask")
+        if mask.numel() != n:
+            raise ValueError("one mask value per point")
+        mcode = DTYPE_F64 if mask.dtype == torch.float64 else DTYPE_F32
+    table = torch.empty((_lib.GAUGE_ROWS, n), dtype=torch.float64, device=device)
+    valid = torch.empty((n,), dtype=torch.uint8, device=device)
+    if n == 0:
+        return table, valid
+    with _on(device):
+        rc = lib.mlx_gauge_prepare(_ptr(lat), _ptr(lon),
+                                   DTYPE_F64 if lat.dtype == torch.float64 else DTYPE_F32,
+                                   _ptr(mask), mcode, n, _ptr(table), _ptr(valid), _stream(device))
+    _lib.check(rc, "mlx_gauge_prepare")
+    return table, valid
+
+
+def _gauge_table(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
+            and t.shape[0] == _lib.GAUGE_ROWS and t.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous (5, n) float64 device table of gauge_prepare")
+    return t
+
+
+def gauge_nearest(points, gauges, split=0):
+    """For every gauge the valid point with the smallest squared chord, ties to the lowest flat
+    index (mlx_gauge_nearest): ``points`` (5, n) and ``gauges`` (5, ng) are tables of
+    ``gauge_prepare``  ->  ``(index (ng) int64, angle (ng) float64)``: the flat index of the
+    winner (-1 when no point is valid) and the haversine angle to it in radians (NaN then).
+    ``split``: into how many parts the points are cut over blocks (0: the library's choice); index
+    and angle are bit-identical for every value."""
+    require_device()
+    lib = _lib.load_gauge()
+    points, gauges = _gauge_table(points, "points"), _gauge_table(gauges, "gauges")
+    if gauges.device != points.device:
+        raise ValueError("points and gauges must live on one device")
+    split = int(split)
+    if split < 0:
+        raise ValueError("split must be >= 0")
+    n, ng, device = points.shape[1], gauges.shape[1], points.device
+    index = torch.full((ng,), -1, dtype=torch.int64, device=device)
+    angle = torch.full((ng,), float("nan"), dtype=torch.float64, device=device)
+    if n == 0 or ng == 0:
+        return index, angle
+    nbytes = lib.mlx_gauge_nearest_workspace_bytes(n, ng, split)
+    if nbytes == 0:
+        raise ValueError(f"{n} points x {ng} gauges is outside the search kernel's range")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=device)
+    with _on(device):
+        rc = lib.mlx_gauge_nearest(_ptr(points), n, _ptr(gauges), ng, split, _ptr(index),
+                                   _ptr(angle), _ptr(ws), nbytes, _stream(device))
+    _lib.check(rc, "mlx_gauge_nearest")
+    return index, angle
+
+
+def gauge_gather(y, index, out=None):
+    """``out[g, r] = y[r, index[g]]`` (mlx_gauge_gather): y (nrest, n) float32 / float64 on the
+    device, ``index`` (ng) integers (host sequence or device tensor)  ->  (ng, nrest) of y's dtype,
+    each gauge's series contiguous, bits copied.  An index outside [0, n) gives a NaN series."""
+    require_device()
+    lib = _lib.load_gauge()
+    if not (isinstance(y, torch.Tensor) and y.is_cuda):
+        raise TypeError("the record must be a device tensor")
+    if y.dim() != 2:
+        raise ValueError("the record must be (nrest, n)")
+    if y.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"the record must be float32 or float64, got {y.dtype}")
+    y = y.contiguous()
+    if isinstance(index, torch.Tensor):
+        if index.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8):
+            raise TypeError("index must hold integers")
+        index = index.to(device=y.device, dtype=torch.int64).reshape(-1).contiguous()
+    else:
+        host = np.asarray(index).reshape(-1)
+        if host.dtype.kind not in "iu":
+            raise TypeError("index must hold integers")
+        index = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int64)).to(y.device)
+    nrest, n = y.shape
+    ng = index.numel()
+    shape = (ng, nrest)
+    if out is None:
+        out = torch.empty(shape, dtype=y.dtype, device=y.device)
+    elif (tuple(out.shape) != shape or out.dtype != y.dtype or out.device != y.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {y.dtype} tensor of shape {shape} on {y.device}")
+    if ng == 0 or nrest == 0:
+        return out
+    if n == 0:
+        return out.fill_(float("nan"))
+    with _on(y.device):
+        rc = lib.mlx_gauge_gather(_ptr(y), DTYPE_F64 if y.dtype == torch.float64 else DTYPE_F32,
+                                  _ptr(index), nrest, n, ng, _ptr(out), _stream(y.device))
+    _lib.check(rc, "mlx_gauge_gather")
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

@@ -18,7 +18,8 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
            os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
-           os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "host_copy.cpp")]
+           os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "momlevel_gauge.hip"),
+           os.path.join(HERE, "host_copy.cpp")]
 DEPENDS = SOURCES + [
     os.path.join(HERE, "eos_device.hpp"),
     os.path.join(HERE, "eos_promote.hpp"),
@@ -26,6 +27,7 @@ DEPENDS = SOURCES + [
     os.path.join(ROOT, "include", "momlevel_hip.h"),
     os.path.join(ROOT, "include", "momlevel_trend.h"),
     os.path.join(ROOT, "include", "momlevel_clim.h"),
+    os.path.join(ROOT, "include", "momlevel_gauge.h"),
     os.path.abspath(__file__),
 ]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
@@ -88,6 +90,13 @@ def clim_source_sha():
     return source_sha([os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "eos_device.hpp"),
                        os.path.join(HERE, "mlx_internal.hpp"),
                        os.path.join(ROOT, "include", "momlevel_clim.h")])
+
+
+def gauge_source_sha():
+    """the tide-gauge kernels' own guard: csrc/momlevel_gauge.hip (+ what it includes, + flags)"""
+    return source_sha([os.path.join(HERE, "momlevel_gauge.hip"), os.path.join(HERE, "eos_device.hpp"),
+                       os.path.join(HERE, "mlx_internal.hpp"),
+                       os.path.join(ROOT, "include", "momlevel_gauge.h")])
 
 
 def hipcc():

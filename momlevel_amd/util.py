@@ -20,10 +20,13 @@ __all__ = [
     "annual_cycle",
     "default_coords",
     "eos_func_from_str",
+    "geolocate_points",
     "linear_detrend",
     "monthly_average",
+    "tile_nominal_coords",
     "validate_areacello",
     "validate_dataset",
+    "validate_tidegauge_data",
 ]
 
 
@@ -282,6 +285,92 @@ def annual_cycle(xobj, tcoord="time", func="mean", time_axis_year=None):
         raise ValueError(f"Unknown argument 'func={func}' to annual cycle")
     plan = climatology.annual_cycle_plan(xobj[tcoord], tcoord, time_axis_year)
     return climatology.grouped_stat(xobj, tcoord, plan, func)
+
+
+# ---------------------------------------------------------------------------------------
+# tide gauges: what tidegauge.extract_tidegauge leans on (util.py:252-367, :620-666, :817-860)
+# ---------------------------------------------------------------------------------------
+@accepts_xarray
+def tile_nominal_coords(xcoord, ycoord, warn=True):
+    """1-D x and y coordinates -> 2-D ``(geolon, geolat)`` with dims ``(ycoord.name, xcoord.name)``
+    (util.py:620-666).  Right for regular lat-lon grids, wrong for the nominal coordinates of an
+    irregular ocean grid -- hence the reference's warning, issued unless ``warn`` is False."""
+    assert isinstance(xcoord, DataArray), "xcoord must be xarray.DataArray"
+    assert isinstance(ycoord, DataArray), "ycoord must be xarray.DataArray"
+    if warn:
+        warnings.warn(
+            "Constructing coordinates from 1-D vectors. "
+            + "Make sure this is the intended behavior. "
+            + "Do not use `xh`/`yh` when `geolon`/`geolat` are available"
+        )
+    xgrp, ygrp = np.meshgrid(xcoord.values, ycoord.values)
+    dims = (ycoord.name, xcoord.name)
+
+    def label(c):
+        return DataArray(c.values, (c.name,), None, c.attrs, c.name)
+
+    coords = {ycoord.name: label(ycoord), xcoord.name: label(xcoord)}
+    return (DataArray(xgrp, dims, coords, None, "geolon"),
+            DataArray(ygrp, dims, coords, None, "geolat"))
+
+
+@accepts_xarray
+def validate_tidegauge_data(arr, xcoord, ycoord, mask):
+    """The argument checks of ``tidegauge.extract_tidegauge`` (util.py:817-860): ``arr`` a
+    DataArray; ``xcoord`` / ``ycoord`` either the name of a coordinate of ``arr`` or a DataArray;
+    ``mask`` a DataArray or None.  ``AssertionError`` otherwise, as in the reference."""
+    assert isinstance(arr, DataArray), "Input array must be `xarray.DataArray` instance"
+    _coords = list(arr.coords)
+    if isinstance(xcoord, str):
+        assert xcoord in _coords, f"`{xcoord}` not found in input array."
+    else:
+        assert isinstance(xcoord, DataArray), (
+            "xcoord must either be a DataArray object or a "
+            + "string that references an existing coordinate"
+        )
+    if isinstance(ycoord, str):
+        assert ycoord in _coords, f"`{ycoord}` not found in input array."
+    else:
+        assert isinstance(ycoord, DataArray), (
+            "ycoord must either be a DataArray object or a "
+            + "string that references an existing coordinate"
+        )
+    if mask is not None:
+        assert isinstance(mask, DataArray), "mask be a DataArray object"
+
+
+def geolocate_points(df_model, df_locs, threshold=None, model_coords=("geolat", "geolon"),
+                     rad_earth=6.378e03, loc_coords=("lat", "lon"), apply_mask=True,
+                     disable_warning=True):
+    """Map real-world locations to their nearest model grid points (util.py:252-367): pandas
+    frames in, a frame out -- ``df_locs`` without its ``lat`` / ``lon`` columns and with
+    ``distance`` (km), ``mod_index`` (the row of the point in the masked model frame),
+    ``model_coords``, ``dim_vals`` (the point's label in the index of ``df_model``) and
+    ``real_coords``.  Rows of ``df_model`` whose ``mask`` is not 1.0 are left out unless
+    ``apply_mask`` is False.
+
+    The reference queries a scikit-learn BallTree; this is ``tidegauge.locate`` -- a brute-force
+    search on the GPU, ties to the lowest row -- and needs pandas only.  With ``threshold=None``
+    nothing is filtered and nothing warned (the reference raises a ``TypeError`` when warnings are
+    enabled without a threshold)."""
+    from . import tidegauge  # (pandas itself is never imported: the frames bring their methods)
+
+    ycoord1, xcoord1 = model_coords
+    ycoord2, xcoord2 = loc_coords
+    df1 = df_model.loc[:, ~df_model.columns.duplicated()]
+    mask = df1["mask"].to_numpy() if (apply_mask and "mask" in df1.columns) else None
+    loc = tidegauge.locate(df1[ycoord1].to_numpy(), df1[xcoord1].to_numpy(),
+                           df_locs[ycoord2].to_numpy(), df_locs[xcoord2].to_numpy(), mask=mask,
+                           threshold=threshold, rad_earth=rad_earth)
+    if not disable_warning and threshold is not None:
+        tidegauge.warn_unmapped(df_locs["name"].tolist(), loc, threshold)
+    df2 = df_locs.iloc[loc.which].copy()
+    df2["distance"] = loc.distance
+    df2["mod_index"] = loc.mod_index
+    df2["model_coords"] = list(zip(*loc.model_coords))
+    df2["dim_vals"] = [df1.index[i] for i in loc.flat_index]
+    df2["real_coords"] = list(zip(df2["lat"].values, df2["lon"].values))
+    return df2.drop(["lat", "lon"], axis=1)
 
 
 def linear_detrend(*args, **kwargs):
