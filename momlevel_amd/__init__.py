@@ -6,7 +6,7 @@ and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, the per-cell trend,
 detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
-include/momlevel_gauge.h).
+include/momlevel_gauge.h, include/momlevel_spice.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -14,7 +14,11 @@ the lowest flat index) and the gauges' series, gathered in one launch -- a devic
 reaches its gauges without a download.  ``util.geolocate_points`` is the same search on pandas
 frames.  The reference's gauge tables are not shipped: pass a CSV path or an in-memory table.
 
-Everything else in momlevel (vorticity, spiciness, ...) is out of scope -- use momlevel.
+``derived.calc_spice`` / ``spice.flament.spice`` map potential temperature and salinity to Flament's
+(2002) spiciness in one pointwise kernel; with ``derived.calc_pdens`` the sigma-pi water-mass view
+is computed without the fields leaving the device.
+
+Everything else in momlevel (vorticity, the Rossby radius, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
 entry points raise ``MomlevelHipError``.
@@ -26,6 +30,7 @@ from . import derived
 from . import dynamic
 from . import eos
 from . import reference
+from . import spice
 from . import test_data
 from . import tidegauge
 from . import timeseries_data
@@ -50,6 +55,7 @@ __all__ = [
     "eos",
     "halosteric",
     "reference",
+    "spice",
     "steric",
     "steric_variants",
     "test_data",

@@ -156,6 +156,13 @@ GAUGE_SIGNATURES = {
 }
 
 
+# The spiciness map (include/momlevel_spice.h): bound by load_spice() on first use, for the same
+# reason.
+SPICE_SIGNATURES = {
+    "mlx_spice_map": (_int, [_vp, _int, _vp, _int, _i64, _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -268,6 +275,29 @@ def load_gauge():
         fn.restype = restype
         fn.argtypes = argtypes
     _gauge_bound = True
+    return lib
+
+
+_spice_bound = False
+
+
+def load_spice():
+    """load(), then declare the prototypes of include/momlevel_spice.h (once); a library built
+    without csrc/momlevel_spice.hip raises ``MomlevelHipError``."""
+    global _spice_bound
+    lib = load()
+    if _spice_bound:
+        return lib
+    for name, (restype, argtypes) in SPICE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise MomlevelHipError(
+                f"{LIB_PATH} does not export {name}: rebuild it with the spiciness kernel "
+                "(`python -m momlevel_amd.csrc.build --force`)") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _spice_bound = True
     return lib
 
 

@@ -1097,6 +1097,36 @@ def gauge_gather(y, index, out=None):
     return out
 
 
+def spice_map(theta, so, out=None):
+    """Flament (2002) spiciness of every cell (mlx_spice_map): ``theta`` and ``so`` contiguous 1-D
+    device tensors of equal length, each float32 or float64 on its own  ->  a float64 device tensor
+    of that length (``out`` when given).  float32 values are widened exactly; all arithmetic is
+    float64."""
+    require_device()
+    lib = _lib.load_spice()
+    for name, x in (("theta", theta), ("so", so)):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise TypeError(f"{name} must be a device tensor")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name} must be float32 or float64, got {x.dtype}")
+        if x.dim() != 1 or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D tensor")
+    if so.numel() != theta.numel() or so.device != theta.device:
+        raise ValueError("theta and so must agree in length and device")
+    n = theta.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=theta.device)
+    elif (tuple(out.shape) != (n,) or out.dtype != torch.float64 or out.device != theta.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 tensor of shape ({n},) on {theta.device}")
+    with _on(theta.device):
+        rc = lib.mlx_spice_map(_ptr(theta), DTYPE_F64 if theta.dtype == torch.float64 else DTYPE_F32,
+                               _ptr(so), DTYPE_F64 if so.dtype == torch.float64 else DTYPE_F32,
+                               n, _ptr(out), _stream(theta.device))
+    _lib.check(rc, "mlx_spice_map")
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
            os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
            os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "momlevel_gauge.hip"),
-           os.path.join(HERE, "host_copy.cpp")]
+           os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "host_copy.cpp")]
 DEPENDS = SOURCES + [
     os.path.join(HERE, "eos_device.hpp"),
     os.path.join(HERE, "eos_promote.hpp"),
@@ -28,6 +28,7 @@ DEPENDS = SOURCES + [
     os.path.join(ROOT, "include", "momlevel_trend.h"),
     os.path.join(ROOT, "include", "momlevel_clim.h"),
     os.path.join(ROOT, "include", "momlevel_gauge.h"),
+    os.path.join(ROOT, "include", "momlevel_spice.h"),
     os.path.abspath(__file__),
 ]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
@@ -97,6 +98,12 @@ def gauge_source_sha():
     return source_sha([os.path.join(HERE, "momlevel_gauge.hip"), os.path.join(HERE, "eos_device.hpp"),
                        os.path.join(HERE, "mlx_internal.hpp"),
                        os.path.join(ROOT, "include", "momlevel_gauge.h")])
+
+
+def spice_source_sha():
+    """the spiciness kernel's own guard: csrc/momlevel_spice.hip (+ what it includes, + flags)"""
+    return source_sha([os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "mlx_internal.hpp"),
+                       os.path.join(ROOT, "include", "momlevel_spice.h")])
 
 
 def hipcc():

@@ -14,7 +14,7 @@ HIP kernel.
 import numpy as np
 import torch
 
-from . import core, engine, hostio, util
+from . import core, engine, hostio, spice, util
 from .adapters import accepts_xarray
 from .labeled import DataArray, is_lazy
 
@@ -28,6 +28,7 @@ __all__ = [
     "calc_pdens",
     "calc_rho",
     "calc_rhoga",
+    "calc_spice",
     "calc_stability_angle",
     "calc_volo",
     "calc_wave_speed",
@@ -109,6 +110,38 @@ def calc_pdens(thetao, so, level=0.0, patm=101325, eos="Wright"):
         "units": "kg m-3",
     }
     return rhopot
+
+
+def _broadcast_full(raw, shape):
+    """``raw`` (an array, tensor or lazy source that broadcasts against ``shape``) at ``shape``"""
+    if tuple(raw.shape) == tuple(shape):
+        return raw
+    return raw.expand(shape) if isinstance(raw, torch.Tensor) else np.broadcast_to(raw, shape)
+
+
+@accepts_xarray
+def calc_spice(thetao, so):
+    """Sea water spiciness after Flament (2002) (derived.py:669-711): thetao in deg C, so in PSU,
+    broadcast against each other by dimension name."""
+    args = [a if isinstance(a, DataArray) else DataArray(np.asarray(a), ()) for a in (thetao, so)]
+    dims = _broadcast_dims(*args)
+    sizes = {}
+    for a in args:
+        sizes.update(a.sizes)
+    shape = tuple(sizes[d] for d in dims)
+    # spice.flament.spice takes equal shapes only: each field is expanded to the common one
+    raw = [_broadcast_full(_expand_to(a, dims, sizes), shape) for a in args]
+    out = spice.flament.spice(*raw)
+    coords = {}
+    for a in args:
+        coords.update(a.coords)
+    pi = DataArray(out, dims, {k: v for k, v in coords.items() if set(v.dims) <= set(dims)})
+    pi.attrs = {
+        "long_name": "Sea water spiciness",
+        "comment": "calculated based on Flament 2002 methodology",
+        "units": "1",
+    }
+    return pi
 
 
 @accepts_xarray

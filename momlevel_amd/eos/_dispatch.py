@@ -82,14 +82,19 @@ _HOST_PIPELINE_ELEMS = 1 << 26
 _HOST_CHUNK_ELEMS = 1 << 25  # 256 MiB of float64 per operand and piece
 
 
-def _evaluate_host_chunked(eos, func, T, S, p, gravity):
+def _host_pipeline(operands, kernel):
     """Large host arrays: walk the leading axis of the broadcast shape in pieces.  Piece k+1 is
     staged and uploaded by a worker thread (hostio.Uploader) while piece k's kernel runs and piece
     k-1's result leaves on another (hostio.Downloader): both directions of the host link are busy
     at once, and the device never holds more than a few pieces (the result is a host array
-    anyway)."""
+    anyway).
+
+    ``operands``: host arrays, lazy sources, python scalars or None (an operand that is absent);
+    ``kernel(ops)``: the per-piece evaluation -- ``ops`` are the operands of one piece in the same
+    order, the arrays among them as device tensors -- returning a device tensor of the piece's
+    shape."""
     arrs = [x if (_is_weak(x) or _is_lazy(x)) else np.asarray(x)
-            for x in (T, S, p if p is not None else 0.0)]
+            for x in (0.0 if x is None else x for x in operands)]
     shape = np.broadcast_shapes(*(_shape(a) for a in arrs))
     rows = max(1, _HOST_CHUNK_ELEMS // max(1, int(np.prod(shape[1:]))))
     bounds = [(i0, min(i0 + rows, shape[0])) for i0 in range(0, shape[0], rows)]
@@ -102,7 +107,7 @@ def _evaluate_host_chunked(eos, func, T, S, p, gravity):
         return hostio.as_plain(a[...]) if _is_lazy(a) else a
 
     def pieces(i0, i1):  # (operands of the piece, which of them travel)
-        ops = [part(arrs[0], i0, i1), part(arrs[1], i0, i1), None if p is None else part(arrs[2], i0, i1)]
+        ops = [None if x is None else part(a, i0, i1) for x, a in zip(operands, arrs)]
         return ops, [k for k, x in enumerate(ops) if x is not None and not _is_weak(x)]
 
     out = None
@@ -120,7 +125,7 @@ def _evaluate_host_chunked(eos, func, T, S, p, gravity):
                 main.wait_event(ready)
                 for k, t in zip(cur_travel, tensors):
                     cur[k] = t
-                res = evaluate(eos, func, cur[0], cur[1], cur[2], gravity=gravity)  # device tensor
+                res = kernel(cur)  # device tensor
                 if out is None:
                     # (a mapping of our own when large, pooled across calls: hostio.result_array)
                     out = hostio.result_array(shape, np.float32 if res.dtype == torch.float32
@@ -129,6 +134,12 @@ def _evaluate_host_chunked(eos, func, T, S, p, gravity):
     finally:
         up.close()
     return out
+
+
+def _evaluate_host_chunked(eos, func, T, S, p, gravity):
+    """f(T, S, p) on large host arrays: the pipeline above with the EOS kernels as its piece"""
+    return _host_pipeline(
+        [T, S, p], lambda ops: evaluate(eos, func, ops[0], ops[1], ops[2], gravity=gravity))
 
 
 def _evaluate_promoted(eos, func, T, S, p, gravity, device, on_device, scalar_in):
