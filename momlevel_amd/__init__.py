@@ -6,7 +6,7 @@ and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, the per-cell trend,
 detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
-include/momlevel_gauge.h, include/momlevel_spice.h).
+include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -18,7 +18,12 @@ frames.  The reference's gauge tables are not shipped: pass a CSV path or an in-
 (2002) spiciness in one pointwise kernel; with ``derived.calc_pdens`` the sigma-pi water-mass view
 is computed without the fields leaving the device.
 
-Everything else in momlevel (vorticity, the Rossby radius, ...) is out of scope -- use momlevel.
+``derived.calc_rel_vort`` / ``calc_pv`` / ``calc_rossby_rd`` (with ``calc_coriolis``) are the
+reference's C-grid group: relative and potential vorticity as horizontal stencils on MOM6's
+staggered grid, one pass each, consuming the N^2 of ``calc_n2`` and the wave speed of
+``calc_wave_speed`` where they were computed.
+
+Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
 entry points raise ``MomlevelHipError``.
@@ -31,6 +36,7 @@ from . import dynamic
 from . import eos
 from . import reference
 from . import spice
+from . import staggered_data
 from . import test_data
 from . import tidegauge
 from . import timeseries_data
@@ -44,6 +50,9 @@ from .steric import halosteric, steric, steric_variants, thermosteric
 # the reference keeps generate_test_data_time in its test_data module; the version with the
 # ``frequency`` argument ("MS" | "D") lives in timeseries_data and is published there
 test_data.generate_test_data_time = timeseries_data.generate_test_data_time
+# generate_test_data_uv (the velocities on the staggered grid) lives in staggered_data and is
+# published where the reference keeps it
+test_data.generate_test_data_uv = staggered_data.generate_test_data_uv
 
 __all__ = [
     "DataArray",

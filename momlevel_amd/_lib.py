@@ -40,6 +40,9 @@ STAT_MEAN, STAT_STD, STAT_MIN, STAT_MAX = range(4)
 # ---- constants mirrored from include/momlevel_gauge.h ------------------------------
 GAUGE_ROW_X, GAUGE_ROW_Y, GAUGE_ROW_Z, GAUGE_ROW_PHI, GAUGE_ROW_LAM = range(5)
 GAUGE_ROWS = 5
+# ---- constants mirrored from include/momlevel_vort.h -------------------------------
+VORT_UNITS_M, VORT_UNITS_CM = 0, 1
+VORT_TILE_LANES, VORT_TILE_H, VORT_TILE_BANDS = 64, 16, 4
 
 
 def flag_tchunk(steps):
@@ -160,6 +163,18 @@ GAUGE_SIGNATURES = {
 # reason.
 SPICE_SIGNATURES = {
     "mlx_spice_map": (_int, [_vp, _int, _vp, _int, _i64, _vp, _vp]),
+}
+
+
+# The vorticity entry points (include/momlevel_vort.h): bound by load_vort() on first use, for the
+# same reason.
+VORT_SIGNATURES = {
+    "mlx_vort_tile_width": (_i64, [_int]),
+    "mlx_vort_rel_vort": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _i64, _i64, _i64, _int, _vp,
+                                 _vp]),
+    "mlx_vort_pv": (_int, [_vp, _int, _vp, _int, _vp, _int, _i64, _i64, _i64, _int, _int, _dbl,
+                           _int, _vp, _vp]),
+    "mlx_vort_rossby": (_int, [_vp, _int, _vp, _int, _i64, _i64, _i64, _vp, _vp]),
 }
 
 
@@ -298,6 +313,29 @@ def load_spice():
         fn.restype = restype
         fn.argtypes = argtypes
     _spice_bound = True
+    return lib
+
+
+_vort_bound = False
+
+
+def load_vort():
+    """load(), then declare the prototypes of include/momlevel_vort.h (once); a library built
+    without csrc/momlevel_vort.hip raises ``MomlevelHipError``."""
+    global _vort_bound
+    lib = load()
+    if _vort_bound:
+        return lib
+    for name, (restype, argtypes) in VORT_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise MomlevelHipError(
+                f"{LIB_PATH} does not export {name}: rebuild it with the vorticity kernels "
+                "(`python -m momlevel_amd.csrc.build --force`)") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _vort_bound = True
     return lib
 
 

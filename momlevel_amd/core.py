@@ -1127,6 +1127,134 @@ def spice_map(theta, so, out=None):
     return out
 
 
+def _vort_operand(x, name, ndim=None):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise TypeError(f"{name} must be a device tensor")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name} must be float32 or float64, got {x.dtype}")
+    if (ndim is not None and x.dim() != ndim) or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {ndim}-D tensor" if ndim is not None
+                         else f"{name} must be contiguous")
+    return DTYPE_F64 if x.dtype == torch.float64 else DTYPE_F32
+
+
+def _vort_out(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if (tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def vort_tile():
+    """(W64, W32, H, bands) of the packed path of the vorticity kernels (include/momlevel_vort.h):
+    a wave's tile is W64 float64 / W32 float32 cells wide and H rows high, a block stacks ``bands``
+    of them in y."""
+    lib = _lib.load_vort()
+    return (int(lib.mlx_vort_tile_width(DTYPE_F64)), int(lib.mlx_vort_tile_width(DTYPE_F32)),
+            _lib.VORT_TILE_H, _lib.VORT_TILE_BANDS)
+
+
+def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
+    """Relative vorticity on the C grid (mlx_vort_rel_vort): ``( -diff_y(u dx) + diff_x(v dy) ) /
+    area`` with zero padding.  ``area`` is the (ny, nx) corner plane; with s = int(symmetric) ``u``
+    is (nrec, ny - s, nx) and ``v`` (nrec, ny, nx - s), both of ONE dtype; ``dx`` / ``dy`` are their
+    2-D metrics, of one dtype with ``area``.  All contiguous device tensors, float32 or float64.
+    Returns (nrec, ny, nx): float32 when fields and metrics are all float32, float64 otherwise --
+    bit for bit what numpy gives operator for operator."""
+    require_device()
+    lib = _lib.load_vort()
+    fdt = _vort_operand(u, "u", 3)
+    if _vort_operand(v, "v", 3) != fdt:
+        raise TypeError(f"u and v must have the same dtype, got {u.dtype} and {v.dtype}")
+    mdt = _vort_operand(area, "area", 2)
+    for name, m in (("dx", dx), ("dy", dy)):
+        if _vort_operand(m, name, 2) != mdt:
+            raise TypeError(f"dx, dy and area must have the same dtype, got {m.dtype} for {name} "
+                            f"and {area.dtype} for area")
+    s = int(bool(symmetric))
+    ny, nx = (int(n) for n in area.shape)
+    nrec = int(u.shape[0])
+    if ny < 1 + s or nx < 1 + s:
+        raise ValueError(f"area {tuple(area.shape)}: the corner plane needs at least {1 + s} points "
+                         "a side")
+    want = {"u": (nrec, ny - s, nx), "v": (nrec, ny, nx - s), "dx": (ny - s, nx), "dy": (ny, nx - s)}
+    for name, x in (("u", u), ("v", v), ("dx", dx), ("dy", dy)):
+        if tuple(x.shape) != want[name]:
+            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {want[name]} for a corner "
+                             f"plane of {(ny, nx)} with symmetric={bool(symmetric)}")
+    if any(x.device != u.device for x in (v, dx, dy, area)):
+        raise ValueError("u, v, dx, dy and area must live on one device")
+    odt = torch.float32 if fdt == DTYPE_F32 and mdt == DTYPE_F32 else torch.float64
+    out = _vort_out(out, (nrec, ny, nx), odt, u.device)
+    with _on(u.device):
+        rc = lib.mlx_vort_rel_vort(_ptr(u), _ptr(v), fdt, _ptr(dx), _ptr(dy), _ptr(area), mdt, nrec,
+                                   ny, nx, s, _ptr(out), _stream(u.device))
+    _lib.check(rc, "mlx_vort_rel_vort")
+    return out
+
+
+VORT_UNITS = {"m": _lib.VORT_UNITS_M, "cm": _lib.VORT_UNITS_CM}
+
+
+def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=False, units="m",
+                        out=None):
+    """Potential vorticity (mlx_vort_pv): ``(zeta + coriolis) * (n2c / gravity)`` and, for
+    ``units="cm"``, ``abs((pv / 100) * 1e14)``.  ``zeta`` (nrec, ny, nx) and ``coriolis`` (ny, nx)
+    live on the corner plane; ``n2`` is (nrec, ny, nx) without ``interp`` and (nrec, ny - s, nx - s)
+    with it (s = int(symmetric)): then n2c is N^2 averaged along x and then along y with zero
+    padding, inside the pass.  Each operand float32 or float64 on its own; the result has numpy's
+    promotion of the three, and numpy's bits."""
+    if units not in VORT_UNITS:
+        raise ValueError(f"unknown units option `{units}`")
+    require_device()
+    lib = _lib.load_vort()
+    zdt, cdt, ndt = (_vort_operand(zeta, "zeta", 3), _vort_operand(coriolis, "coriolis", 2),
+                     _vort_operand(n2, "n2", 3))
+    interp = int(bool(interp))
+    s = int(bool(symmetric)) if interp else 0
+    nrec, ny, nx = (int(n) for n in zeta.shape)
+    if tuple(coriolis.shape) != (ny, nx):
+        raise ValueError(f"coriolis has shape {tuple(coriolis.shape)}, expected {(ny, nx)}")
+    if ny < 1 + s or nx < 1 + s:
+        raise ValueError(f"zeta {tuple(zeta.shape)}: the corner plane needs at least {1 + s} points "
+                         "a side")
+    if tuple(n2.shape) != (nrec, ny - s, nx - s):
+        raise ValueError(f"n2 has shape {tuple(n2.shape)}, expected {(nrec, ny - s, nx - s)} for "
+                         f"zeta {tuple(zeta.shape)} with interp={bool(interp)}, "
+                         f"symmetric={bool(symmetric)}")
+    if coriolis.device != zeta.device or n2.device != zeta.device:
+        raise ValueError("zeta, coriolis and n2 must live on one device")
+    odt = torch.float32 if (zdt, cdt, ndt) == (DTYPE_F32,) * 3 else torch.float64
+    out = _vort_out(out, (nrec, ny, nx), odt, zeta.device)
+    with _on(zeta.device):
+        rc = lib.mlx_vort_pv(_ptr(zeta), zdt, _ptr(coriolis), cdt, _ptr(n2), ndt, nrec, ny, nx,
+                             interp, s, float(gravity), VORT_UNITS[units], _ptr(out),
+                             _stream(zeta.device))
+    _lib.check(rc, "mlx_vort_pv")
+    return out
+
+
+def rossby_radius(c, f, out=None):
+    """``c / abs(f)`` (mlx_vort_rossby): ``c`` a contiguous (outer, plane, inner) device tensor, ``f``
+    a contiguous tensor of ``plane`` elements, each float32 or float64; IEEE division, so that
+    ``f == 0`` gives the +-inf / NaN numpy gives."""
+    require_device()
+    lib = _lib.load_vort()
+    cdt, fdt = _vort_operand(c, "c", 3), _vort_operand(f, "f")
+    outer, plane, inner = (int(n) for n in c.shape)
+    if f.numel() != plane or f.device != c.device:
+        raise ValueError(f"f must hold {plane} elements on {c.device}")
+    odt = torch.float32 if (cdt, fdt) == (DTYPE_F32, DTYPE_F32) else torch.float64
+    out = _vort_out(out, (outer, plane, inner), odt, c.device)
+    with _on(c.device):
+        rc = lib.mlx_vort_rossby(_ptr(c), cdt, _ptr(f), fdt, outer, plane, inner, _ptr(out),
+                                 _stream(c.device))
+    _lib.check(rc, "mlx_vort_rossby")
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

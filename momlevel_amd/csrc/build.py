@@ -19,7 +19,8 @@ ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
            os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
            os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "momlevel_gauge.hip"),
-           os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "host_copy.cpp")]
+           os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "momlevel_vort.hip"),
+           os.path.join(HERE, "host_copy.cpp")]
 DEPENDS = SOURCES + [
     os.path.join(HERE, "eos_device.hpp"),
     os.path.join(HERE, "eos_promote.hpp"),
@@ -29,6 +30,7 @@ DEPENDS = SOURCES + [
     os.path.join(ROOT, "include", "momlevel_clim.h"),
     os.path.join(ROOT, "include", "momlevel_gauge.h"),
     os.path.join(ROOT, "include", "momlevel_spice.h"),
+    os.path.join(ROOT, "include", "momlevel_vort.h"),
     os.path.abspath(__file__),
 ]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
@@ -104,6 +106,12 @@ def spice_source_sha():
     """the spiciness kernel's own guard: csrc/momlevel_spice.hip (+ what it includes, + flags)"""
     return source_sha([os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "mlx_internal.hpp"),
                        os.path.join(ROOT, "include", "momlevel_spice.h")])
+
+
+def vort_source_sha():
+    """the vorticity kernels' own guard: csrc/momlevel_vort.hip (+ what it includes, + flags)"""
+    return source_sha([os.path.join(HERE, "momlevel_vort.hip"), os.path.join(HERE, "mlx_internal.hpp"),
+                       os.path.join(ROOT, "include", "momlevel_vort.h")])
 
 
 def hipcc():

@@ -6,7 +6,9 @@ Same signatures as src/momlevel/derived.py: ``calc_rho`` (:597-639), ``calc_mass
 kernel, and their consumers: ``calc_n2`` (:328-411),
 ``calc_stability_angle`` (:714-766), ``adjust_negative_n2`` (:30-71) and
 ``calc_wave_speed`` (:798-831), each ONE pass of a HIP kernel of its own
-(csrc/momlevel_strat.hip) over what the reference evaluates as dozens of numpy passes.  Inputs and outputs are labelled arrays (momlevel_amd.labeled, or xarray
+(csrc/momlevel_strat.hip) over what the reference evaluates as dozens of numpy passes; and the
+C-grid group ``calc_rel_vort`` (:187-246), ``calc_pv`` (:489-565), ``calc_rossby_rd`` (:568-594)
+on the stencil kernels of csrc/momlevel_vort.hip, with ``calc_coriolis`` (:162-184).  Inputs and outputs are labelled arrays (momlevel_amd.labeled, or xarray
 objects when xarray is installed -- see adapters.py); every number comes from a
 HIP kernel.
 """
@@ -16,18 +18,22 @@ import torch
 
 from . import core, engine, hostio, spice, util
 from .adapters import accepts_xarray
-from .labeled import DataArray, is_lazy
+from .labeled import DataArray, check_field_dtype, is_lazy
 
 __all__ = [
     "adjust_negative_n2",
     "calc_alpha",
     "calc_beta",
+    "calc_coriolis",
     "calc_dz",
     "calc_masso",
     "calc_n2",
     "calc_pdens",
+    "calc_pv",
+    "calc_rel_vort",
     "calc_rho",
     "calc_rhoga",
+    "calc_rossby_rd",
     "calc_spice",
     "calc_stability_angle",
     "calc_volo",
@@ -351,41 +357,56 @@ _HOST_PIPELINE_ELEMS = 1 << 26
 _HOST_GROUP_ELEMS = 1 << 25
 
 
+def _host_leading_groups(fields, nlead, rows, dev, kernel, out):
+    """``kernel`` on host fields, group of leading rows by group: the rows are independent, so
+    group k+1 uploads (hostio.Uploader) while group k's kernel runs and group k-1's result leaves
+    (hostio.Downloader), and the device never holds more than a few groups.  ``fields`` are sliced
+    along their own leading axis (length ``nlead``) as they are -- a lazy field (dask / netCDF4 /
+    h5py-like) is read group by group in the upload worker and never materialised whole;
+    ``kernel(tensors, i0, i1)`` returns the device result of rows [i0, i1), which lands in
+    ``out[i0:i1]``."""
+    bounds = [(i0, min(i0 + rows, nlead)) for i0 in range(0, nlead, rows)]
+    main = torch.cuda.current_stream(dev)
+    up = hostio.Uploader(dev)
+    try:
+        with hostio.Downloader(dev) as results:
+            nxt = up.submit([hostio.leading_slice(f, *bounds[0]) for f in fields])
+            for n, (i0, i1) in enumerate(bounds):
+                tensors, ready = nxt.result()  # (re-raises what the worker raised)
+                if n + 1 < len(bounds):
+                    j0, j1 = bounds[n + 1]
+                    nxt = up.submit([hostio.leading_slice(f, j0, j1) for f in fields])
+                main.wait_event(ready)
+                res = kernel(tensors, i0, i1)
+                results.submit([(out[i0:i1], res.reshape(out[i0:i1].shape))])
+    finally:
+        up.close()
+    return out
+
+
 def _stratification_host_rows(T, S, p, z, nt, nz, plane, dev, lead=None, **kw):
-    """core.stratification on host fields seen as (nt, nz, plane), group of rows by group: rows
-    are independent (the derivative runs along z), so group k+1 uploads (hostio.Uploader) while
-    group k's kernel runs and group k-1's result leaves (hostio.Downloader).  ``lead``: the
+    """core.stratification on host fields seen as (nt, nz, plane), group of rows by group
+    (_host_leading_groups: rows are independent, the derivative runs along z).  ``lead``: the
     fields are (lead, nz, ...) with ONE dimension before z (the usual (time, z, y, x)): they are
-    then sliced along it as they are -- a lazy field (dask / netCDF4 / h5py-like) is read group by
-    group in the upload worker and never materialised whole.  (A pressure that varies from row to
-    row -- ``p`` of shape (nt, nz, plane) -- IS resident whole: _strat_pressure expanded it before
-    the groups start; only theta/S and the result are streamed.)"""
+    then sliced along it as they are -- a lazy field is read group by group and never materialised
+    whole.  (A pressure that varies from row to row -- ``p`` of shape (nt, nz, plane) -- IS
+    resident whole: _strat_pressure expanded it before the groups start; only theta/S and the
+    result are streamed.)"""
     if lead is not None:
         Tn, Sn = T, S  # sliced along their own leading axis
     else:
         Tn = hostio.as_plain(T[...] if is_lazy(T) else T).reshape(nt, nz, plane)
         Sn = hostio.as_plain(S[...] if is_lazy(S) else S).reshape(nt, nz, plane)
     rows = max(1, _HOST_GROUP_ELEMS // (nz * plane))
-    bounds = [(i0, min(i0 + rows, nt)) for i0 in range(0, nt, rows)]
     p_rows = isinstance(p, torch.Tensor) and p.dim() == 3  # a pressure that varies from row to row
-    out = np.empty((nt, nz, plane), dtype=np.float64)
-    main = torch.cuda.current_stream(dev)
-    up = hostio.Uploader(dev)
-    try:
-        with hostio.Downloader(dev) as results:
-            nxt = up.submit([hostio.leading_slice(Tn, *bounds[0]), hostio.leading_slice(Sn, *bounds[0])])
-            for n, (i0, i1) in enumerate(bounds):
-                (Td, Sd), ready = nxt.result()  # (re-raises what the worker raised)
-                if n + 1 < len(bounds):
-                    j0, j1 = bounds[n + 1]
-                    nxt = up.submit([hostio.leading_slice(Tn, j0, j1), hostio.leading_slice(Sn, j0, j1)])
-                main.wait_event(ready)
-                res = core.stratification(Td.reshape(i1 - i0, nz, plane), Sd.reshape(i1 - i0, nz, plane),
-                                          p[i0:i1] if p_rows else p, z, **kw)
-                results.submit([(out[i0:i1], res)])
-    finally:
-        up.close()
-    return out
+
+    def kernel(tensors, i0, i1):
+        Td, Sd = tensors
+        return core.stratification(Td.reshape(i1 - i0, nz, plane), Sd.reshape(i1 - i0, nz, plane),
+                                   p[i0:i1] if p_rows else p, z, **kw)
+
+    return _host_leading_groups([Tn, Sn], nt, rows, dev, kernel,
+                                np.empty((nt, nz, plane), dtype=np.float64))
 
 
 @accepts_xarray
@@ -485,3 +506,254 @@ def calc_wave_speed(n2, dz, zcoord="z_l"):
         "units": "m s-1",
     }
     return result
+
+
+# ---------------------------------------------------------------------------------------
+# vorticity on the staggered (C) grid: the stencils of csrc/momlevel_vort.hip
+# ---------------------------------------------------------------------------------------
+_COORD_KEYS = ("xcenter", "ycenter", "xcorner", "ycorner")
+
+
+def _coord_names(coord_dict):
+    """the four dimension names of util.get_xgcm_grid (util.py:424-430); the grid object itself is
+    not built (no xgcm): the names say which dimension is which"""
+    if coord_dict is None:
+        return {"xcenter": "xh", "ycenter": "yh", "xcorner": "xq", "ycorner": "yq"}
+    missing = [k for k in _COORD_KEYS if k not in coord_dict]
+    if missing:
+        raise ValueError(f"coord_dict is missing the keys {missing}")
+    return {k: coord_dict[k] for k in _COORD_KEYS}
+
+
+def _float_name(da, what, allow_other=False):
+    """"float32" / "float64"; float16, long double (check_field_dtype) and, unless
+    ``allow_other``, everything that is not a float are refused"""
+    name = check_field_dtype(da.dtype, what)
+    if name not in ("float32", "float64"):
+        if not allow_other:
+            raise TypeError(f"{what} must be float32 or float64, not {name}")
+        name = "float64"
+    return name
+
+
+def _trailing(da, ydim, xdim, what):
+    if len(da.dims) < 2 or tuple(da.dims[-2:]) != (ydim, xdim):
+        raise ValueError(f"{what} has dims {da.dims}: its last two must be ({ydim!r}, {xdim!r}), "
+                         "in that order")
+
+
+def _corner_extents(sizes, names, symmetric, what):
+    """(ny, nx) of the corner plane after checking centre against corner lengths"""
+    s = int(bool(symmetric))
+    for c, q in (("ycenter", "ycorner"), ("xcenter", "xcorner")):
+        nc, nq = sizes.get(names[c]), sizes.get(names[q])
+        if nc is not None and nq is not None and nq != nc + s:
+            raise ValueError(
+                f"{what}: {names[q]!r} has {nq} points and {names[c]!r} has {nc}; a "
+                f"{'symmetric' if s else 'non-symmetric'} grid needs {nc + s} corner points "
+                f"(symmetric={bool(symmetric)})")
+    return sizes[names["ycorner"]], sizes[names["xcorner"]]
+
+
+def _raw(da):
+    """numpy (a lazy source is read whole) or the device tensor"""
+    return da.data if da.is_device else da.values
+
+
+def _records(x, dev, dtype, nrec, tail):
+    return engine.to_device(x, dev, dtype).reshape((nrec,) + tuple(tail)).contiguous()
+
+
+def _stencil(fields, lead_shape, out_tail, out_np_dtype, dev, on_device, kernel):
+    """``kernel(tensors)`` on the (nrec, y, x) views of ``fields`` (labelled arrays that share
+    ``lead_shape``), whole or -- large host / lazy fields with more than one leading row -- in
+    groups of whole leading rows (_host_leading_groups).  Returns the raw result at
+    lead_shape + out_tail: host in, host out."""
+    shape = tuple(lead_shape) + tuple(out_tail)
+    nrec = int(np.prod(lead_shape, dtype=np.int64))
+    tdt = [torch.float32 if str(f.dtype) == "float32" else torch.float64 for f in fields]
+
+    def views(tensors, n):
+        return [t.reshape((n,) + tuple(f.shape[-2:])) for t, f in zip(tensors, fields)]
+
+    if (not on_device and len(lead_shape) >= 1 and lead_shape[0] > 1
+            and int(np.prod(shape, dtype=np.int64)) > _HOST_PIPELINE_ELEMS):
+        inner = int(np.prod(lead_shape[1:], dtype=np.int64))
+        rows = max(1, _HOST_GROUP_ELEMS // max(1, int(np.prod(shape[1:], dtype=np.int64))))
+        sources = [f.data if f.is_lazy else f.values for f in fields]
+        out = np.empty(shape, dtype=out_np_dtype)
+        return _host_leading_groups(
+            sources, lead_shape[0], rows, dev,
+            lambda tensors, i0, i1: kernel(views([t.to(d) for t, d in zip(tensors, tdt)],
+                                                 (i1 - i0) * inner)), out)
+    tensors = [_records(_raw(f), dev, d, nrec, f.shape[-2:]) for f, d in zip(fields, tdt)]
+    res = kernel(tensors).reshape(shape)
+    return res if on_device else hostio.to_host(res)
+
+
+@accepts_xarray
+def calc_coriolis(lat):
+    """Coriolis parameter ``2 (2 pi / 86400) sin(lat pi / 180)`` (derived.py:162-184).  Evaluated
+    by numpy ON THE HOST: a 2-D field computed once per grid, and the bits of libm's ``sin`` cannot
+    be pinned on the device.  A device-resident ``lat`` is downloaded and the result returned on
+    its device."""
+    if not isinstance(lat, DataArray):
+        lat = DataArray(np.asarray(lat))
+    values = lat.values
+    coriolis = 2.0 * (2.0 * np.pi / (60.0 * 60.0 * 24.0)) * np.sin(values * np.pi / 180.0)
+    data = engine.to_device(coriolis, lat.data.device) if lat.is_device else coriolis
+    return DataArray(data, lat.dims, dict(lat.coords), {
+        "standard_name": "coriolis_parameter",
+        "long_name": "Coriolis parameter",
+        "units": "s-1",
+    }, None)
+
+
+@accepts_xarray
+def calc_rel_vort(dset, varname_map=None, coord_dict=None, symmetric=False):
+    """Vertical component of the relative vorticity on the corner points (derived.py:187-246):
+    ``( -diff_y(uo * dxCu) + diff_x(vo * dyCv) ) / areacello_bu`` with xgcm's zero-filled
+    differences, ONE pass of core.rel_vort.  ``coord_dict`` names the four horizontal dimensions
+    (the keys of util.get_xgcm_grid).  The two horizontal dimensions must be the last two of each
+    field, y then x; ``uo`` and ``vo`` share a dtype (float32 or float64), the three metrics too."""
+    if varname_map is None:
+        varname_map = {"u": "uo", "v": "vo", "dx": "dxCu", "dy": "dyCv", "area": "areacello_bu"}
+    missing = list(set(varname_map.values()) - set(dset.variables))
+    if len(missing) > 0:
+        raise ValueError(f"Input dataset missing fields: {missing}")
+    names = _coord_names(coord_dict)
+    u, v, dx, dy, area = (dset[varname_map[k]] for k in ("u", "v", "dx", "dy", "area"))
+    yc, xc, yq, xq = names["ycenter"], names["xcenter"], names["ycorner"], names["xcorner"]
+    _trailing(u, yc, xq, varname_map["u"])
+    _trailing(v, yq, xc, varname_map["v"])
+    for m, dims, what in ((dx, (yc, xq), varname_map["dx"]), (dy, (yq, xc), varname_map["dy"]),
+                          (area, (yq, xq), varname_map["area"])):
+        if tuple(m.dims) != dims:
+            raise ValueError(f"{what} has dims {m.dims}: expected {dims}")
+    if tuple(u.dims[:-2]) != tuple(v.dims[:-2]) or tuple(u.shape[:-2]) != tuple(v.shape[:-2]):
+        raise ValueError(f"{varname_map['u']} {u.dims}{tuple(u.shape)} and {varname_map['v']} "
+                         f"{v.dims}{tuple(v.shape)} must share their leading dims")
+    sizes = {}
+    for a in (u, v, dx, dy, area):
+        for d, n in zip(a.dims[-2:], a.shape[-2:]):
+            if sizes.setdefault(d, n) != n:
+                raise ValueError(f"{d!r} has {n} points in one field and {sizes[d]} in another")
+    ny, nx = _corner_extents(sizes, names, symmetric, "calc_rel_vort")
+    fdt = _float_name(u, "velocity fields")
+    if _float_name(v, "velocity fields") != fdt:
+        raise TypeError(f"{varname_map['u']} is {u.dtype} and {varname_map['v']} is {v.dtype}: "
+                        "convert one of them")
+    mdts = {_float_name(m, "grid metrics") for m in (dx, dy, area)}
+    if len(mdts) != 1:
+        raise TypeError(f"{varname_map['dx']}, {varname_map['dy']} and {varname_map['area']} must "
+                        f"share one dtype, not {sorted(mdts)}")
+    mdt = mdts.pop()
+    dev = engine.device_of(u.data, v.data, dx.data, dy.data, area.data)
+    on_device = u.is_device or v.is_device
+    mt = torch.float32 if mdt == "float32" else torch.float64
+    dxd, dyd, aread = (engine.to_device(_raw(m), dev, mt).contiguous() for m in (dx, dy, area))
+    out_dtype = np.float32 if (fdt, mdt) == ("float32", "float32") else np.float64
+    out = _stencil([u, v], tuple(u.shape[:-2]), (ny, nx), out_dtype, dev, on_device,
+                   lambda t: core.rel_vort(t[0], t[1], dxd, dyd, aread, symmetric=symmetric))
+    dims = tuple(u.dims[:-2]) + (yq, xq)
+    coords = {k: c for k, c in dset.coords.items() if set(c.dims) <= set(dims)}
+    return DataArray(out, dims, coords, {
+        "standard_name": "ocean_relative_vorticity",
+        "long_name": "Ocean relative vorticity",
+        "units": "s-1",
+    })
+
+
+@accepts_xarray
+def calc_pv(zeta, coriolis, n2, gravity=9.8, coord_dict=None, symmetric=False, units="m",
+            interp_n2=True):
+    """Ocean potential vorticity ``(zeta + coriolis) * (n2 / gravity)`` (derived.py:489-565), N^2
+    averaged to the corner points first (``interp_n2``: along x, then along y, zero-filled --
+    xgcm's ``grid.interp(n2, axis=["X", "Y"], boundary="fill")``) inside the same pass of
+    core.potential_vorticity.  ``units="cm"`` gives ``abs((pv / 100) * 1e14)``.  ``zeta`` and
+    ``n2`` share their leading dims; ``gravity`` is a python float (it takes N^2's dtype)."""
+    if units not in core.VORT_UNITS:
+        raise ValueError(f"unknown units option `{units}`")
+    names = _coord_names(coord_dict)
+    yc, xc, yq, xq = names["ycenter"], names["xcenter"], names["ycorner"], names["xcorner"]
+    interp = bool(interp_n2)
+    if interp:
+        _trailing(zeta, yq, xq, "zeta")
+        _trailing(n2, yc, xc, "n2")
+        if tuple(coriolis.dims) != (yq, xq):
+            raise ValueError(f"coriolis has dims {coriolis.dims}: expected {(yq, xq)}")
+    else:
+        if len(zeta.dims) < 2 or tuple(n2.dims[-2:]) != tuple(zeta.dims[-2:]):
+            raise ValueError(f"without interp_n2, n2 {n2.dims} must lie on the points of zeta "
+                             f"{zeta.dims}")
+        if tuple(coriolis.dims) != tuple(zeta.dims[-2:]):
+            raise ValueError(f"coriolis has dims {coriolis.dims}: expected {tuple(zeta.dims[-2:])}")
+    if tuple(zeta.dims[:-2]) != tuple(n2.dims[:-2]) or tuple(zeta.shape[:-2]) != tuple(n2.shape[:-2]):
+        raise ValueError(f"zeta {zeta.dims}{tuple(zeta.shape)} and n2 {n2.dims}{tuple(n2.shape)} "
+                         "must share their leading dims")
+    if tuple(coriolis.shape) != tuple(zeta.shape[-2:]):
+        raise ValueError(f"coriolis {tuple(coriolis.shape)} does not cover zeta's plane "
+                         f"{tuple(zeta.shape[-2:])}")
+    ny, nx = (int(n) for n in zeta.shape[-2:])
+    if interp:
+        sizes = {yq: ny, xq: nx, yc: int(n2.shape[-2]), xc: int(n2.shape[-1])}
+        _corner_extents(sizes, names, symmetric, "calc_pv")
+    elif tuple(n2.shape[-2:]) != (ny, nx):
+        raise ValueError(f"n2 {tuple(n2.shape)} and zeta {tuple(zeta.shape)} differ in shape")
+    zdt, ndt = _float_name(zeta, "zeta"), _float_name(n2, "n2")
+    cdt = _float_name(coriolis, "coriolis", allow_other=True)
+    dev = engine.device_of(zeta.data, n2.data, coriolis.data)
+    on_device = zeta.is_device or n2.is_device
+    fd = engine.to_device(_raw(coriolis), dev,
+                          torch.float32 if cdt == "float32" else torch.float64).contiguous()
+    out_dtype = np.float32 if (zdt, cdt, ndt) == ("float32",) * 3 else np.float64
+    out = _stencil([zeta, n2], tuple(zeta.shape[:-2]), (ny, nx), out_dtype, dev, on_device,
+                   lambda t: core.potential_vorticity(t[0], fd, t[1], gravity=float(gravity),
+                                                      interp=interp, symmetric=symmetric,
+                                                      units=units))
+    coords = dict(coriolis.coords)
+    coords.update(zeta.coords)
+    pv = DataArray(out, zeta.dims, {k: c for k, c in coords.items() if set(c.dims) <= set(zeta.dims)})
+    pv.attrs = {
+        "long_name": "Ocean potential vorticity",
+        "units": "m-1 s-1" if units == "m" else "10^14 cm-1 s-1",
+    }
+    return pv
+
+
+@accepts_xarray
+def calc_rossby_rd(wave_speed, coriolis):
+    """Rossby radius of deformation ``wave_speed / abs(coriolis)`` (derived.py:568-594), the
+    Coriolis parameter broadcast by dimension name: its dims must be a contiguous run of
+    ``wave_speed``'s -- (yh, xh) of (yh, xh), of (time, yh, xh) or of the (z_l, yh, xh, time) array
+    calc_wave_speed returns for 4-D input.  IEEE division: at the equator the result is the
+    ``inf`` / NaN numpy gives."""
+    nd = len(coriolis.dims)
+    start = None
+    for k in range(len(wave_speed.dims) - nd + 1):
+        if tuple(wave_speed.dims[k:k + nd]) == tuple(coriolis.dims):
+            start = k
+            break
+    if start is None:
+        raise ValueError(f"coriolis dims {coriolis.dims} are not a contiguous run of wave_speed's "
+                         f"{wave_speed.dims}")
+    if tuple(wave_speed.shape[start:start + nd]) != tuple(coriolis.shape):
+        raise ValueError(f"coriolis {coriolis.dims}{tuple(coriolis.shape)} does not fit wave_speed "
+                         f"{wave_speed.dims}{tuple(wave_speed.shape)}")
+    shape = tuple(int(n) for n in wave_speed.shape)
+    outer = int(np.prod(shape[:start], dtype=np.int64))
+    plane = int(np.prod(shape[start:start + nd], dtype=np.int64))
+    inner = int(np.prod(shape[start + nd:], dtype=np.int64))
+    wdt = _float_name(wave_speed, "wave_speed", allow_other=True)
+    cdt = _float_name(coriolis, "coriolis", allow_other=True)
+    dev = engine.device_of(wave_speed.data, coriolis.data)
+    c = engine.to_device(_raw(wave_speed), dev, torch.float32 if wdt == "float32" else torch.float64)
+    f = engine.to_device(_raw(coriolis), dev, torch.float32 if cdt == "float32" else torch.float64)
+    out = core.rossby_radius(c.contiguous().reshape(outer, plane, inner),
+                             f.contiguous().reshape(plane)).reshape(shape)
+    on_device = wave_speed.is_device or coriolis.is_device
+    coords = dict(coriolis.coords)
+    coords.update(wave_speed.coords)
+    return DataArray(out if on_device else hostio.to_host(out), wave_speed.dims,
+                     {k: v for k, v in coords.items() if set(v.dims) <= set(wave_speed.dims)},
+                     {"long name": "Rossby radius of deformation", "units": "m"}, None)
