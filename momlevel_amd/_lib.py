@@ -182,6 +182,20 @@ class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
 
+def _declare(lib, table, rebuild_with=None):
+    """Declare the prototypes of ``table`` on ``lib``; a missing symbol raises ``MomlevelHipError``
+    (with ``rebuild_with``: naming the kernels the library was built without)."""
+    for name, (restype, argtypes) in table.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            hint = "" if rebuild_with is None else (
+                f": rebuild it with {rebuild_with} (`python -m momlevel_amd.csrc.build --force`)")
+            raise MomlevelHipError(f"{LIB_PATH} does not export {name}{hint}") from exc
+        fn.restype = restype
+        fn.argtypes = argtypes
+
+
 _lib = None
 
 
@@ -204,13 +218,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise MomlevelHipError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(f"{LIB_PATH} does not export {name}") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _declare(lib, SIGNATURES)
     if lib.mlx_version() != ABI_VERSION:
         raise MomlevelHipError(
             f"ABI mismatch: library {lib.mlx_version()} vs binding {ABI_VERSION}; rebuild"
@@ -224,119 +232,49 @@ def load():
     return lib
 
 
-_trend_bound = False
+# group -> (the table of include/momlevel_<group>.h, what csrc/momlevel_<group>.hip adds)
+_GROUPS = {
+    "trend": (TREND_SIGNATURES, "the trend kernels"),
+    "clim": (CLIM_SIGNATURES, "the grouped-statistic kernel"),
+    "gauge": (GAUGE_SIGNATURES, "the tide-gauge kernels"),
+    "spice": (SPICE_SIGNATURES, "the spiciness kernel"),
+    "vort": (VORT_SIGNATURES, "the vorticity kernels"),
+}
+
+
+# what is bound: one module flag per group (the host tests reset them by name)
+_trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = False
+
+
+def _load_group(group):
+    """load(), then declare the prototypes of include/momlevel_<group>.h (once); a library built
+    without csrc/momlevel_<group>.hip raises ``MomlevelHipError``."""
+    lib = load()
+    flag = f"_{group}_bound"
+    if not globals().get(flag, False):  # (a group without a flag of its own above starts unbound)
+        _declare(lib, *_GROUPS[group])
+        globals()[flag] = True
+    return lib
 
 
 def load_trend():
-    """load(), then declare the prototypes of include/momlevel_trend.h (once); a library built
-    without csrc/momlevel_trend.hip raises ``MomlevelHipError``."""
-    global _trend_bound
-    lib = load()
-    if _trend_bound:
-        return lib
-    for name, (restype, argtypes) in TREND_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(
-                f"{LIB_PATH} does not export {name}: rebuild it with the trend kernels "
-                "(`python -m momlevel_amd.csrc.build --force`)") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _trend_bound = True
-    return lib
-
-
-_clim_bound = False
+    return _load_group("trend")
 
 
 def load_clim():
-    """load(), then declare the prototypes of include/momlevel_clim.h (once); a library built
-    without csrc/momlevel_clim.hip raises ``MomlevelHipError``."""
-    global _clim_bound
-    lib = load()
-    if _clim_bound:
-        return lib
-    for name, (restype, argtypes) in CLIM_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(
-                f"{LIB_PATH} does not export {name}: rebuild it with the grouped-statistic kernel "
-                "(`python -m momlevel_amd.csrc.build --force`)") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _clim_bound = True
-    return lib
-
-
-_gauge_bound = False
+    return _load_group("clim")
 
 
 def load_gauge():
-    """load(), then declare the prototypes of include/momlevel_gauge.h (once); a library built
-    without csrc/momlevel_gauge.hip raises ``MomlevelHipError``."""
-    global _gauge_bound
-    lib = load()
-    if _gauge_bound:
-        return lib
-    for name, (restype, argtypes) in GAUGE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(
-                f"{LIB_PATH} does not export {name}: rebuild it with the tide-gauge kernels "
-                "(`python -m momlevel_amd.csrc.build --force`)") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _gauge_bound = True
-    return lib
-
-
-_spice_bound = False
+    return _load_group("gauge")
 
 
 def load_spice():
-    """load(), then declare the prototypes of include/momlevel_spice.h (once); a library built
-    without csrc/momlevel_spice.hip raises ``MomlevelHipError``."""
-    global _spice_bound
-    lib = load()
-    if _spice_bound:
-        return lib
-    for name, (restype, argtypes) in SPICE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(
-                f"{LIB_PATH} does not export {name}: rebuild it with the spiciness kernel "
-                "(`python -m momlevel_amd.csrc.build --force`)") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _spice_bound = True
-    return lib
-
-
-_vort_bound = False
+    return _load_group("spice")
 
 
 def load_vort():
-    """load(), then declare the prototypes of include/momlevel_vort.h (once); a library built
-    without csrc/momlevel_vort.hip raises ``MomlevelHipError``."""
-    global _vort_bound
-    lib = load()
-    if _vort_bound:
-        return lib
-    for name, (restype, argtypes) in VORT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise MomlevelHipError(
-                f"{LIB_PATH} does not export {name}: rebuild it with the vorticity kernels "
-                "(`python -m momlevel_amd.csrc.build --force`)") from exc
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _vort_bound = True
-    return lib
+    return _load_group("vort")
 
 
 def last_error():

@@ -109,6 +109,39 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _call(lib, name, device, *args):
+    """One launch of the C ABI: ``lib.<name>(*args, stream)`` on torch's current stream of
+    ``device``, with ``device`` current; a non-zero status raises ``MomlevelHipError``."""
+    with _on(device):
+        rc = getattr(lib, name)(*args, _stream(device))
+    _lib.check(rc, name)
+
+
+def _float_code(x, name, ndim=None):
+    """The dtype code of an operand the kernels read in place: a contiguous (``ndim``-D, when
+    given) float32 or float64 device tensor."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise TypeError(f"{name} must be a device tensor")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name} must be float32 or float64, got {x.dtype}")
+    if (ndim is not None and x.dim() != ndim) or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {ndim}-D tensor" if ndim is not None
+                         else f"{name} must be contiguous")
+    return DTYPE_F64 if x.dtype == torch.float64 else DTYPE_F32
+
+
+def _out_like(out, shape, dtype, device, noun=None):
+    """``out`` when it is a contiguous ``dtype`` tensor of ``shape`` on ``device``; a new one for
+    None.  ``noun``: how the error text names the dtype (default: as torch prints it)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if (tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {noun or dtype} tensor of shape {tuple(shape)} "
+                         f"on {device}")
+    return out
+
+
 def _f64(x, device):
     """Small time-invariant operand -> contiguous float64 device tensor."""
     if isinstance(x, torch.Tensor) and x.is_cuda:
@@ -223,12 +256,8 @@ def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=No
     flags = (_arith_flag(arith, "k0", dt)
              if (func == "density" and eos.lower() == "wright") else 0)
     out = torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=T.device)
-    with _on(T.device):
-        rc = _lib.load().mlx_eos_map(
-            _ptr(T), _ptr(S), dt, _ptr(pt), p_mode, EOS_IDS[eos.lower()], FUNC_IDS[func],
-            nt, nz, ny * nx, sT, sS, flags, _ptr(out), _stream(T.device),
-        )
-    _lib.check(rc, "mlx_eos_map")
+    _call(_lib.load(), "mlx_eos_map", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), p_mode,
+          EOS_IDS[eos.lower()], FUNC_IDS[func], nt, nz, ny * nx, sT, sS, flags, _ptr(out))
     return out[0] if squeeze else out
 
 
@@ -238,12 +267,8 @@ def inverse_barometer(T, S, p, gravity=9.8, eos="wright", f32_mode="faithful"):
     T, S, nt, nz, ny, nx, sT, sS, dt, squeeze = _pair(T, S, f32_mode)
     pt, p_mode = _pressure(p, nt, nz, ny, nx, T.device, allow4d=True)
     out = torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=T.device)
-    with _on(T.device):
-        rc = _lib.load().mlx_inverse_barometer(
-            _ptr(T), _ptr(S), dt, _ptr(pt), p_mode, EOS_IDS[eos.lower()], float(gravity),
-            nt, nz, ny * nx, sT, sS, _ptr(out), _stream(T.device),
-        )
-    _lib.check(rc, "mlx_inverse_barometer")
+    _call(_lib.load(), "mlx_inverse_barometer", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), p_mode,
+          EOS_IDS[eos.lower()], float(gravity), nt, nz, ny * nx, sT, sS, _ptr(out))
     return out[0] if squeeze else out
 
 
@@ -291,10 +316,8 @@ def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8):
         fid = FUNC_IDS[func]
     out = torch.empty(n, dtype=torch.float64, device=device)
     kind = ctypes.c_int(-1)
-    with _on(device):
-        rc = _lib.load().mlx_eos_map_promote(*args, EOS_IDS[eos.lower()], fid, float(gravity), n,
-                                             _ptr(out), ctypes.byref(kind), _stream(device))
-    _lib.check(rc, "mlx_eos_map_promote")
+    _call(_lib.load(), "mlx_eos_map_promote", device, *args, EOS_IDS[eos.lower()], fid,
+          float(gravity), n, _ptr(out), ctypes.byref(kind))
     if kind.value == _lib.KIND_F32:  # the kernel stored n float32 values at the start of the buffer
         return out.view(torch.float32)[:n]
     return out
@@ -378,13 +401,9 @@ def stratification(T, S, p, z, func="n2", eos="wright", gravity=-9.8, f32_mode="
                              f"({nt},{nz},{plane})")
     coef_dev = _f64(coef, T.device)
     out = torch.empty((nt, nz, plane), dtype=torch.float64, device=T.device)
-    with _on(T.device):
-        rc = _lib.load().mlx_stratification(
-            _ptr(T), _ptr(S), dt, _ptr(pt), *strides, EOS_IDS[eos.lower()],
-            {"n2": _lib.STRAT_N2, "turner": _lib.STRAT_TURNER}[func], _ptr(coef_dev),
-            int(uniform), float(two_dx), float(gravity), nt, nz, plane, _ptr(out),
-            _stream(T.device))
-    _lib.check(rc, "mlx_stratification")
+    _call(_lib.load(), "mlx_stratification", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), *strides,
+          EOS_IDS[eos.lower()], {"n2": _lib.STRAT_N2, "turner": _lib.STRAT_TURNER}[func],
+          _ptr(coef_dev), int(uniform), float(two_dx), float(gravity), nt, nz, plane, _ptr(out))
     return out
 
 
@@ -404,11 +423,8 @@ def adjust_negative_n2(n2, lead0_rows, dz=None, want_adjusted=True):
         if tuple(dzt.shape) != (nz, plane):
             raise ValueError(f"dz has shape {tuple(dzt.shape)}, expected {(nz, plane)}")
         speed = torch.empty((nt, plane), dtype=torch.float64, device=n2.device)
-    with _on(n2.device):
-        rc = _lib.load().mlx_adjust_negative_n2(_ptr(n2), nt, nz, plane, int(lead0_rows),
-                                                _ptr(dzt), _ptr(adjusted), _ptr(speed),
-                                                _stream(n2.device))
-    _lib.check(rc, "mlx_adjust_negative_n2")
+    _call(_lib.load(), "mlx_adjust_negative_n2", n2.device, _ptr(n2), nt, nz, plane,
+          int(lead0_rows), _ptr(dzt), _ptr(adjusted), _ptr(speed))
     return adjusted, speed
 
 
@@ -420,10 +436,8 @@ def wave_speed_where_time0(n2_t0, speed):
     nt = int(speed.shape[0])
     out = torch.empty((nz, plane, nt), dtype=torch.float64, device=speed.device)
     n2_t0, speed = n2_t0.contiguous(), speed.contiguous()
-    with _on(speed.device):
-        rc = _lib.load().mlx_wave_speed_where_time0(_ptr(n2_t0), _ptr(speed), nt, nz, plane,
-                                                    _ptr(out), _stream(speed.device))
-    _lib.check(rc, "mlx_wave_speed_where_time0")
+    _call(_lib.load(), "mlx_wave_speed_where_time0", speed.device, _ptr(n2_t0), _ptr(speed), nt, nz,
+          plane, _ptr(out))
     return out
 
 
@@ -522,10 +536,7 @@ def stream_probe(a, b, out=None):
     require_device()
     if out is None:
         out = torch.empty_like(a)
-    with _on(a.device):
-        rc = _lib.load().mlx_stream_probe(_ptr(a), _ptr(b), a.numel(), _ptr(out),
-                                          _stream(a.device))
-    _lib.check(rc, "mlx_stream_probe")
+    _call(_lib.load(), "mlx_stream_probe", a.device, _ptr(a), _ptr(b), a.numel(), _ptr(out))
     return out
 
 
@@ -539,10 +550,8 @@ def stream_probe_mix(a, b=None, out=None, write=True):
         raise ValueError("a and b must agree in dtype and size")
     if out is None:
         out = torch.empty(a.shape if write else (1,), dtype=torch.float64, device=a.device)
-    with _on(a.device):
-        rc = _lib.load().mlx_stream_probe_mix(_ptr(a), _ptr(b), dt, a.numel(), _ptr(out),
-                                              int(bool(write)), _stream(a.device))
-    _lib.check(rc, "mlx_stream_probe_mix")
+    _call(_lib.load(), "mlx_stream_probe_mix", a.device, _ptr(a), _ptr(b), dt, a.numel(), _ptr(out),
+          int(bool(write)))
     return out
 
 
@@ -555,9 +564,7 @@ def valu_probe(iters=4096, device="cuda"):
 
     out = torch.zeros(1, dtype=torch.float64, device=device)
     n = ctypes.c_int64(0)
-    with _on(device):
-        rc = _lib.load().mlx_valu_probe(int(iters), _ptr(out), ctypes.byref(n), _stream(device))
-    _lib.check(rc, "mlx_valu_probe")
+    _call(_lib.load(), "mlx_valu_probe", device, int(iters), _ptr(out), ctypes.byref(n))
     return int(n.value)
 
 
@@ -567,10 +574,8 @@ def fold_mask(rho0, vol0):
     rho0 = _f64(rho0, rho0.device)
     vol0 = _f64(vol0, rho0.device)
     out = torch.empty_like(rho0)
-    with _on(rho0.device):
-        rc = _lib.load().mlx_fold_mask(_ptr(rho0), _ptr(vol0), rho0.numel(), _ptr(out),
-                                       _stream(rho0.device))
-    _lib.check(rc, "mlx_fold_mask")
+    _call(_lib.load(), "mlx_fold_mask", rho0.device, _ptr(rho0), _ptr(vol0), rho0.numel(),
+          _ptr(out))
     return out
 
 
@@ -614,13 +619,10 @@ def _steric_local(entry, T, S, held, rho0m, vol0_surface, p, neg_inv_rhozero, dz
             raise ValueError("z_i must have nz+1 entries and deptho be (ny,nx)")
 
     def launch(*outputs):
-        with _on(dev):
-            rc = getattr(_lib.load(), entry)(
-                _ptr(T), _ptr(S), *map(_ptr, held or ()), dt, _ptr(rho0m), _ptr(vol0_surface),
-                _ptr(dz), _ptr(z_i), _ptr(deptho), _ptr(pt), p_mode, EOS_IDS[eos.lower()],
-                float(neg_inv_rhozero), nt, nz, ny * nx, sT, sS, flags, *outputs, _stream(dev),
-            )
-        _lib.check(rc, entry)
+        _call(_lib.load(), entry, dev, _ptr(T), _ptr(S), *map(_ptr, held or ()), dt, _ptr(rho0m),
+              _ptr(vol0_surface), _ptr(dz), _ptr(z_i), _ptr(deptho), _ptr(pt), p_mode,
+              EOS_IDS[eos.lower()], float(neg_inv_rhozero), nt, nz, ny * nx, sT, sS, flags,
+              *outputs)
 
     return dev, (nt, nz, ny, nx), launch
 
@@ -702,9 +704,7 @@ def nansum(x):
     nbytes = lib.mlx_nansum_workspace_bytes(x.numel())
     ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=x.device)
     out = torch.empty(1, dtype=torch.float64, device=x.device)
-    with _on(x.device):
-        rc = lib.mlx_nansum(_ptr(x), x.numel(), _ptr(out), _ptr(ws), nbytes, _stream(x.device))
-    _lib.check(rc, "mlx_nansum")
+    _call(lib, "mlx_nansum", x.device, _ptr(x), x.numel(), _ptr(out), _ptr(ws), nbytes)
     return out[0]
 
 
@@ -729,11 +729,8 @@ def masso(rho, vol):
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=rho.device)
     for t0 in range(0, nt, step):
         t1 = min(t0 + step, nt)
-        with _on(rho.device):
-            rc = lib.mlx_masso(_ptr(rho[t0:t1]), _ptr(vol[t0:t1] if vstride else vol), t1 - t0,
-                               n3, vstride, _ptr(out[t0:t1]), _ptr(ws), nbytes,
-                               _stream(rho.device))
-        _lib.check(rc, "mlx_masso")
+        _call(lib, "mlx_masso", rho.device, _ptr(rho[t0:t1]), _ptr(vol[t0:t1] if vstride else vol),
+              t1 - t0, n3, vstride, _ptr(out[t0:t1]), _ptr(ws), nbytes)
     return out
 
 
@@ -750,10 +747,8 @@ def group_weighted_mean(x, w, group_len, out=None):
     n = x[0].numel()
     if out is None:
         out = torch.empty((ngroups,) + tuple(x.shape[1:]), dtype=torch.float64, device=x.device)
-    with _on(x.device):
-        rc = _lib.load().mlx_group_weighted_mean(_ptr(x), _ptr(w), ngroups, group_len, n,
-                                                 _ptr(out), _stream(x.device))
-    _lib.check(rc, "mlx_group_weighted_mean")
+    _call(_lib.load(), "mlx_group_weighted_mean", x.device, _ptr(x), _ptr(w), ngroups, group_len, n,
+          _ptr(out))
     return out
 
 
@@ -777,7 +772,7 @@ def _time_record(y):
     if y.dtype not in (torch.float32, torch.float64):
         y = y.to(torch.float64)
     y = y.contiguous()
-    return y, y.shape[0], y[0].numel(), (DTYPE_F64 if y.dtype == torch.float64 else DTYPE_F32)
+    return y, y.shape[0], y[0].numel(), _float_code(y, "the record")
 
 
 def _fit_workspace(lib, nt, n, nterms, device):
@@ -802,10 +797,8 @@ def time_linfit(y, xt, s, xmean):
     if n == 0:
         return slope, intercept
     ws, nbytes = _fit_workspace(lib, nt, n, 5, y.device)
-    with _on(y.device):
-        rc = lib.mlx_time_linfit(_ptr(y), code, _ptr(xt), nt, n, float(s), float(xmean),
-                                 _ptr(slope), _ptr(intercept), _ptr(ws), nbytes, _stream(y.device))
-    _lib.check(rc, "mlx_time_linfit")
+    _call(lib, "mlx_time_linfit", y.device, _ptr(y), code, _ptr(xt), nt, n, float(s), float(xmean),
+          _ptr(slope), _ptr(intercept), _ptr(ws), nbytes)
     return slope, intercept
 
 
@@ -823,10 +816,8 @@ def time_project(y, P):
     if n == 0:
         return coef
     ws, nbytes = _fit_workspace(lib, nt, n, K, y.device)
-    with _on(y.device):
-        rc = lib.mlx_time_project(_ptr(y), code, _ptr(P), K, nt, n, _ptr(coef), _ptr(ws), nbytes,
-                                  _stream(y.device))
-    _lib.check(rc, "mlx_time_project")
+    _call(lib, "mlx_time_project", y.device, _ptr(y), code, _ptr(P), K, nt, n, _ptr(coef), _ptr(ws),
+          nbytes)
     return coef
 
 
@@ -877,11 +868,8 @@ def time_apply(y, mode, xm, a, b=None, out=None):
             xs = xm[t0:t1]
             if mode == "trend_anom" and t0:
                 raise ValueError("trend_anom: time axis too long for one call")
-        with _on(device):
-            rc = lib.mlx_time_apply(_ptr(y[t0:t1]) if reads_y else None, code, code_mode, _ptr(xs),
-                                    _ptr(a), _ptr(b), K, t1 - t0, n, _ptr(out[t0:t1]),
-                                    _stream(device))
-        _lib.check(rc, "mlx_time_apply")
+        _call(lib, "mlx_time_apply", device, _ptr(y[t0:t1]) if reads_y else None, code, code_mode,
+              _ptr(xs), _ptr(a), _ptr(b), K, t1 - t0, n, _ptr(out[t0:t1]))
     return out
 
 
@@ -948,18 +936,11 @@ def time_group_stat(y, steps, offsets=None, stat="mean", out=None):
     else:
         groups = DeviceGroups(steps, offsets, nt, y.device)
     shape = (groups.ngroups,) + tuple(y.shape[1:])
-    if out is None:
-        out = torch.empty(shape, dtype=y.dtype, device=y.device)
-    elif (tuple(out.shape) != shape or out.dtype != y.dtype or out.device != y.device
-          or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {y.dtype} tensor of shape {shape} on {y.device}")
+    out = _out_like(out, shape, y.dtype, y.device)
     if n == 0:
         return out
-    with _on(y.device):
-        rc = lib.mlx_clim_group_stat(_ptr(y), code, _ptr(groups.steps), _ptr(groups.offsets),
-                                     groups.nsel, groups.ngroups, nt, n, STAT_IDS[stat], _ptr(out),
-                                     _stream(y.device))
-    _lib.check(rc, "mlx_clim_group_stat")
+    _call(lib, "mlx_clim_group_stat", y.device, _ptr(y), code, _ptr(groups.steps),
+          _ptr(groups.offsets), groups.nsel, groups.ngroups, nt, n, STAT_IDS[stat], _ptr(out))
     return out
 
 
@@ -1005,16 +986,13 @@ def gauge_prepare(lat, lon, mask=None, device=None):
         mask = _gauge_operand(mask, device, "mask")
         if mask.numel() != n:
             raise ValueError("one mask value per point")
-        mcode = DTYPE_F64 if mask.dtype == torch.float64 else DTYPE_F32
+        mcode = _float_code(mask, "mask")
     table = torch.empty((_lib.GAUGE_ROWS, n), dtype=torch.float64, device=device)
     valid = torch.empty((n,), dtype=torch.uint8, device=device)
     if n == 0:
         return table, valid
-    with _on(device):
-        rc = lib.mlx_gauge_prepare(_ptr(lat), _ptr(lon),
-                                   DTYPE_F64 if lat.dtype == torch.float64 else DTYPE_F32,
-                                   _ptr(mask), mcode, n, _ptr(table), _ptr(valid), _stream(device))
-    _lib.check(rc, "mlx_gauge_prepare")
+    _call(lib, "mlx_gauge_prepare", device, _ptr(lat), _ptr(lon), _float_code(lat, "lat"),
+          _ptr(mask), mcode, n, _ptr(table), _ptr(valid))
     return table, valid
 
 
@@ -1049,10 +1027,8 @@ def gauge_nearest(points, gauges, split=0):
     if nbytes == 0:
         raise ValueError(f"{n} points x {ng} gauges is outside the search kernel's range")
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=device)
-    with _on(device):
-        rc = lib.mlx_gauge_nearest(_ptr(points), n, _ptr(gauges), ng, split, _ptr(index),
-                                   _ptr(angle), _ptr(ws), nbytes, _stream(device))
-    _lib.check(rc, "mlx_gauge_nearest")
+    _call(lib, "mlx_gauge_nearest", device, _ptr(points), n, _ptr(gauges), ng, split, _ptr(index),
+          _ptr(angle), _ptr(ws), nbytes)
     return index, angle
 
 
@@ -1062,13 +1038,11 @@ def gauge_gather(y, index, out=None):
     each gauge's series contiguous, bits copied.  An index outside [0, n) gives a NaN series."""
     require_device()
     lib = _lib.load_gauge()
-    if not (isinstance(y, torch.Tensor) and y.is_cuda):
-        raise TypeError("the record must be a device tensor")
-    if y.dim() != 2:
-        raise ValueError("the record must be (nrest, n)")
-    if y.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"the record must be float32 or float64, got {y.dtype}")
-    y = y.contiguous()
+    if isinstance(y, torch.Tensor) and y.is_cuda:
+        if y.dim() != 2:
+            raise ValueError("the record must be (nrest, n)")
+        y = y.contiguous()  # (a strided record is copied, not refused)
+    code = _float_code(y, "the record")
     if isinstance(index, torch.Tensor):
         if index.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8):
             raise TypeError("index must hold integers")
@@ -1081,19 +1055,12 @@ def gauge_gather(y, index, out=None):
     nrest, n = y.shape
     ng = index.numel()
     shape = (ng, nrest)
-    if out is None:
-        out = torch.empty(shape, dtype=y.dtype, device=y.device)
-    elif (tuple(out.shape) != shape or out.dtype != y.dtype or out.device != y.device
-          or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {y.dtype} tensor of shape {shape} on {y.device}")
+    out = _out_like(out, shape, y.dtype, y.device)
     if ng == 0 or nrest == 0:
         return out
     if n == 0:
         return out.fill_(float("nan"))
-    with _on(y.device):
-        rc = lib.mlx_gauge_gather(_ptr(y), DTYPE_F64 if y.dtype == torch.float64 else DTYPE_F32,
-                                  _ptr(index), nrest, n, ng, _ptr(out), _stream(y.device))
-    _lib.check(rc, "mlx_gauge_gather")
+    _call(lib, "mlx_gauge_gather", y.device, _ptr(y), code, _ptr(index), nrest, n, ng, _ptr(out))
     return out
 
 
@@ -1104,46 +1071,12 @@ def spice_map(theta, so, out=None):
     float64."""
     require_device()
     lib = _lib.load_spice()
-    for name, x in (("theta", theta), ("so", so)):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            raise TypeError(f"{name} must be a device tensor")
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{name} must be float32 or float64, got {x.dtype}")
-        if x.dim() != 1 or not x.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous 1-D tensor")
+    tdt, sdt = _float_code(theta, "theta", 1), _float_code(so, "so", 1)
     if so.numel() != theta.numel() or so.device != theta.device:
         raise ValueError("theta and so must agree in length and device")
     n = theta.numel()
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=theta.device)
-    elif (tuple(out.shape) != (n,) or out.dtype != torch.float64 or out.device != theta.device
-          or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous float64 tensor of shape ({n},) on {theta.device}")
-    with _on(theta.device):
-        rc = lib.mlx_spice_map(_ptr(theta), DTYPE_F64 if theta.dtype == torch.float64 else DTYPE_F32,
-                               _ptr(so), DTYPE_F64 if so.dtype == torch.float64 else DTYPE_F32,
-                               n, _ptr(out), _stream(theta.device))
-    _lib.check(rc, "mlx_spice_map")
-    return out
-
-
-def _vort_operand(x, name, ndim=None):
-    if not (isinstance(x, torch.Tensor) and x.is_cuda):
-        raise TypeError(f"{name} must be a device tensor")
-    if x.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"{name} must be float32 or float64, got {x.dtype}")
-    if (ndim is not None and x.dim() != ndim) or not x.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {ndim}-D tensor" if ndim is not None
-                         else f"{name} must be contiguous")
-    return DTYPE_F64 if x.dtype == torch.float64 else DTYPE_F32
-
-
-def _vort_out(out, shape, dtype, device):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if (tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    out = _out_like(out, (n,), torch.float64, theta.device, "float64")
+    _call(lib, "mlx_spice_map", theta.device, _ptr(theta), tdt, _ptr(so), sdt, n, _ptr(out))
     return out
 
 
@@ -1165,12 +1098,12 @@ def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
     bit for bit what numpy gives operator for operator."""
     require_device()
     lib = _lib.load_vort()
-    fdt = _vort_operand(u, "u", 3)
-    if _vort_operand(v, "v", 3) != fdt:
+    fdt = _float_code(u, "u", 3)
+    if _float_code(v, "v", 3) != fdt:
         raise TypeError(f"u and v must have the same dtype, got {u.dtype} and {v.dtype}")
-    mdt = _vort_operand(area, "area", 2)
+    mdt = _float_code(area, "area", 2)
     for name, m in (("dx", dx), ("dy", dy)):
-        if _vort_operand(m, name, 2) != mdt:
+        if _float_code(m, name, 2) != mdt:
             raise TypeError(f"dx, dy and area must have the same dtype, got {m.dtype} for {name} "
                             f"and {area.dtype} for area")
     s = int(bool(symmetric))
@@ -1187,11 +1120,9 @@ def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
     if any(x.device != u.device for x in (v, dx, dy, area)):
         raise ValueError("u, v, dx, dy and area must live on one device")
     odt = torch.float32 if fdt == DTYPE_F32 and mdt == DTYPE_F32 else torch.float64
-    out = _vort_out(out, (nrec, ny, nx), odt, u.device)
-    with _on(u.device):
-        rc = lib.mlx_vort_rel_vort(_ptr(u), _ptr(v), fdt, _ptr(dx), _ptr(dy), _ptr(area), mdt, nrec,
-                                   ny, nx, s, _ptr(out), _stream(u.device))
-    _lib.check(rc, "mlx_vort_rel_vort")
+    out = _out_like(out, (nrec, ny, nx), odt, u.device)
+    _call(lib, "mlx_vort_rel_vort", u.device, _ptr(u), _ptr(v), fdt, _ptr(dx), _ptr(dy), _ptr(area),
+          mdt, nrec, ny, nx, s, _ptr(out))
     return out
 
 
@@ -1210,8 +1141,8 @@ def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=
         raise ValueError(f"unknown units option `{units}`")
     require_device()
     lib = _lib.load_vort()
-    zdt, cdt, ndt = (_vort_operand(zeta, "zeta", 3), _vort_operand(coriolis, "coriolis", 2),
-                     _vort_operand(n2, "n2", 3))
+    zdt, cdt, ndt = (_float_code(zeta, "zeta", 3), _float_code(coriolis, "coriolis", 2),
+                     _float_code(n2, "n2", 3))
     interp = int(bool(interp))
     s = int(bool(symmetric)) if interp else 0
     nrec, ny, nx = (int(n) for n in zeta.shape)
@@ -1227,12 +1158,9 @@ def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=
     if coriolis.device != zeta.device or n2.device != zeta.device:
         raise ValueError("zeta, coriolis and n2 must live on one device")
     odt = torch.float32 if (zdt, cdt, ndt) == (DTYPE_F32,) * 3 else torch.float64
-    out = _vort_out(out, (nrec, ny, nx), odt, zeta.device)
-    with _on(zeta.device):
-        rc = lib.mlx_vort_pv(_ptr(zeta), zdt, _ptr(coriolis), cdt, _ptr(n2), ndt, nrec, ny, nx,
-                             interp, s, float(gravity), VORT_UNITS[units], _ptr(out),
-                             _stream(zeta.device))
-    _lib.check(rc, "mlx_vort_pv")
+    out = _out_like(out, (nrec, ny, nx), odt, zeta.device)
+    _call(lib, "mlx_vort_pv", zeta.device, _ptr(zeta), zdt, _ptr(coriolis), cdt, _ptr(n2), ndt,
+          nrec, ny, nx, interp, s, float(gravity), VORT_UNITS[units], _ptr(out))
     return out
 
 
@@ -1242,16 +1170,14 @@ def rossby_radius(c, f, out=None):
     ``f == 0`` gives the +-inf / NaN numpy gives."""
     require_device()
     lib = _lib.load_vort()
-    cdt, fdt = _vort_operand(c, "c", 3), _vort_operand(f, "f")
+    cdt, fdt = _float_code(c, "c", 3), _float_code(f, "f")
     outer, plane, inner = (int(n) for n in c.shape)
     if f.numel() != plane or f.device != c.device:
         raise ValueError(f"f must hold {plane} elements on {c.device}")
     odt = torch.float32 if (cdt, fdt) == (DTYPE_F32, DTYPE_F32) else torch.float64
-    out = _vort_out(out, (outer, plane, inner), odt, c.device)
-    with _on(c.device):
-        rc = lib.mlx_vort_rossby(_ptr(c), cdt, _ptr(f), fdt, outer, plane, inner, _ptr(out),
-                                 _stream(c.device))
-    _lib.check(rc, "mlx_vort_rossby")
+    out = _out_like(out, (outer, plane, inner), odt, c.device)
+    _call(lib, "mlx_vort_rossby", c.device, _ptr(c), cdt, _ptr(f), fdt, outer, plane, inner,
+          _ptr(out))
     return out
 
 
@@ -1263,13 +1189,9 @@ def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     nz = z_i.numel() - 1
     ny, nx = depth.shape
     out = torch.empty((nz, ny, nx), dtype=torch.float64, device=depth.device)
-    with _on(depth.device):
-        rc = _lib.load().mlx_calc_dz(
-            _ptr(z_i), _ptr(depth), nz, ny * nx, float(top),
-            float(bottom) if bottom is not None else 0.0, int(bottom is not None),
-            int(bool(fraction)), _ptr(out), _stream(depth.device),
-        )
-    _lib.check(rc, "mlx_calc_dz")
+    _call(_lib.load(), "mlx_calc_dz", depth.device, _ptr(z_i), _ptr(depth), nz, ny * nx, float(top),
+          float(bottom) if bottom is not None else 0.0, int(bottom is not None),
+          int(bool(fraction)), _ptr(out))
     return out
 
 
@@ -1284,10 +1206,6 @@ def synth_field(shape, dtype=torch.float64, *, seed, field_id, lo, scale, mask3d
     code = DTYPE_F64 if out.dtype == torch.float64 else DTYPE_F32
     if mask3d is not None:
         mask3d = _f64(mask3d, out.device)
-    with _on(out.device):
-        rc = _lib.load().mlx_synth_field(
-            _ptr(out), code, nt, nz, ny, nx, t0, NY, NX, origin[0], origin[1], seed, field_id,
-            float(lo), float(scale), _ptr(mask3d), _stream(out.device),
-        )
-    _lib.check(rc, "mlx_synth_field")
+    _call(_lib.load(), "mlx_synth_field", out.device, _ptr(out), code, nt, nz, ny, nx, t0, NY, NX,
+          origin[0], origin[1], seed, field_id, float(lo), float(scale), _ptr(mask3d))
     return out

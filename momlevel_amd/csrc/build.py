@@ -16,23 +16,29 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
-SOURCES = [os.path.join(HERE, "momlevel_hip.hip"), os.path.join(HERE, "momlevel_promote.hip"),
-           os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "momlevel_trend.hip"),
-           os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "momlevel_gauge.hip"),
-           os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "momlevel_vort.hip"),
-           os.path.join(HERE, "host_copy.cpp")]
-DEPENDS = SOURCES + [
-    os.path.join(HERE, "eos_device.hpp"),
-    os.path.join(HERE, "eos_promote.hpp"),
-    os.path.join(HERE, "mlx_internal.hpp"),
-    os.path.join(ROOT, "include", "momlevel_hip.h"),
-    os.path.join(ROOT, "include", "momlevel_trend.h"),
-    os.path.join(ROOT, "include", "momlevel_clim.h"),
-    os.path.join(ROOT, "include", "momlevel_gauge.h"),
-    os.path.join(ROOT, "include", "momlevel_spice.h"),
-    os.path.join(ROOT, "include", "momlevel_vort.h"),
-    os.path.abspath(__file__),
-]
+_TIMED_UNITS = ["momlevel_hip.hip", "momlevel_promote.hip"]
+# feature -> what its translation unit csrc/momlevel_<feature>.hip includes, in the order its sha
+# hashes them.  One row per feature: SOURCES, DEPENDS and <feature>_source_sha() follow.
+FEATURES = {
+    "strat": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp"],
+    "trend": ["eos_device.hpp", "mlx_internal.hpp", "include/momlevel_trend.h"],
+    "clim": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_clim.h"],
+    "gauge": ["eos_device.hpp", "mlx_internal.hpp", "include/momlevel_gauge.h"],
+    "spice": ["mlx_internal.hpp", "include/momlevel_spice.h"],
+    "vort": ["mlx_internal.hpp", "include/momlevel_vort.h"],
+}
+
+
+def _path(name):
+    return os.path.join(ROOT, name) if name.startswith("include/") else os.path.join(HERE, name)
+
+
+def _feature_files(feature):
+    return [_path(f"momlevel_{feature}.hip")] + [_path(name) for name in FEATURES[feature]]
+
+
+SOURCES = [_path(name) for name in _TIMED_UNITS + [f"momlevel_{f}.hip" for f in FEATURES]
+           + ["host_copy.cpp"]]
 LIB = os.path.join(PKG, "libmomlevel_hip.so")
 
 FLAGS = [
@@ -59,6 +65,9 @@ TIMED_SOURCES = [
     os.path.join(HERE, "eos_promote.hpp"),
     os.path.join(ROOT, "include", "momlevel_hip.h"),
 ]
+# what the library is rebuilt for: every source and header above, and this file
+DEPENDS = sorted({*SOURCES, *TIMED_SOURCES, *(p for f in FEATURES for p in _feature_files(f)),
+                  os.path.abspath(__file__)})
 
 
 def source_sha(paths=None, flags=True):
@@ -75,43 +84,39 @@ def source_sha(paths=None, flags=True):
     return h.hexdigest()[:16]
 
 
+def feature_source_sha(feature):
+    """a feature's own guard: csrc/momlevel_<feature>.hip (+ what it includes, + flags)"""
+    return source_sha(_feature_files(feature))
+
+
 def strat_source_sha():
     """the stratification kernels' own guard: csrc/momlevel_strat.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_strat.hip"), os.path.join(HERE, "eos_device.hpp"),
-                       os.path.join(HERE, "mlx_internal.hpp")])
+    return feature_source_sha("strat")
 
 
 def trend_source_sha():
     """the trend kernels' own guard: csrc/momlevel_trend.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_trend.hip"), os.path.join(HERE, "eos_device.hpp"),
-                       os.path.join(HERE, "mlx_internal.hpp"),
-                       os.path.join(ROOT, "include", "momlevel_trend.h")])
+    return feature_source_sha("trend")
 
 
 def clim_source_sha():
     """the grouped-statistic kernel's own guard: csrc/momlevel_clim.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_clim.hip"), os.path.join(HERE, "eos_device.hpp"),
-                       os.path.join(HERE, "mlx_internal.hpp"),
-                       os.path.join(ROOT, "include", "momlevel_clim.h")])
+    return feature_source_sha("clim")
 
 
 def gauge_source_sha():
     """the tide-gauge kernels' own guard: csrc/momlevel_gauge.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_gauge.hip"), os.path.join(HERE, "eos_device.hpp"),
-                       os.path.join(HERE, "mlx_internal.hpp"),
-                       os.path.join(ROOT, "include", "momlevel_gauge.h")])
+    return feature_source_sha("gauge")
 
 
 def spice_source_sha():
     """the spiciness kernel's own guard: csrc/momlevel_spice.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_spice.hip"), os.path.join(HERE, "mlx_internal.hpp"),
-                       os.path.join(ROOT, "include", "momlevel_spice.h")])
+    return feature_source_sha("spice")
 
 
 def vort_source_sha():
     """the vorticity kernels' own guard: csrc/momlevel_vort.hip (+ what it includes, + flags)"""
-    return source_sha([os.path.join(HERE, "momlevel_vort.hip"), os.path.join(HERE, "mlx_internal.hpp"),
-                       os.path.join(ROOT, "include", "momlevel_vort.h")])
+    return feature_source_sha("vort")
 
 
 def hipcc():

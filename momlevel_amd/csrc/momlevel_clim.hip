@@ -33,6 +33,7 @@
 #include "../../include/momlevel_clim.h"
 #include "eos_device.hpp"
 #include "mlx_internal.hpp"
+#include "mlx_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -43,53 +44,11 @@ constexpr int kClimBlock = 256;  // 4 waves of 64
 constexpr int kClimUnroll = 8;   // row packs a lane has in flight
 constexpr unsigned kClimMaxGridY = 65535;
 
-typedef float cf4_t __attribute__((ext_vector_type(4)));
-typedef float cf2_t __attribute__((ext_vector_type(2)));
-
-template <typename T, int V>
-struct CPack {
-  T v[V];
-};
-
-// once-read data moves with the `nt` cache policy (the idiom of momlevel_hip.hip's load_pack):
-// one global_load_dword / dwordx2 / dwordx4 per lane
-template <typename TIn, int V>
-__device__ __forceinline__ CPack<TIn, V> cl_load(const TIn* __restrict__ p) {
-  CPack<TIn, V> r;
-  if constexpr (V == 1) {
-    r.v[0] = __builtin_nontemporal_load(p);
-  } else if constexpr (sizeof(TIn) == 4 && V == 2) {
-    cf2_t raw = __builtin_nontemporal_load(reinterpret_cast<const cf2_t*>(p));
-    r.v[0] = raw.x;
-    r.v[1] = raw.y;
-  } else {
-    static_assert(sizeof(TIn) * V == 16, "a pack is at most 16 bytes");
-    cf4_t raw = __builtin_nontemporal_load(reinterpret_cast<const cf4_t*>(p));
-    __builtin_memcpy(&r, &raw, 16);
-  }
-  return r;
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void cl_store(T* __restrict__ p, const CPack<T, V>& r) {
-  if constexpr (V == 1) {
-    p[0] = r.v[0];
-  } else if constexpr (sizeof(T) == 4 && V == 2) {
-    cf2_t raw = {r.v[0], r.v[1]};
-    *reinterpret_cast<cf2_t*>(p) = raw;
-  } else {
-    static_assert(sizeof(T) * V == 16, "a pack is at most 16 bytes");
-    cf4_t raw;
-    __builtin_memcpy(&raw, &r, 16);
-    *reinterpret_cast<cf4_t*>(p) = raw;
-  }
-}
-
 // The row of step index s, widened to float64.  s is wave-uniform.  An index outside [0, nt) --
 // a caller's mistake the entry point cannot see -- reads row 0 and yields NaN: never out of bounds.
 template <typename TIn, int V>
 struct Row {
-  CPack<TIn, V> raw;
+  Pack<TIn, V> raw;
   bool ok;
   __device__ __forceinline__ double at(int k) const {
     return ok ? (double)raw.v[k] : canonical_nan();  // float32 -> float64 is exact
@@ -101,7 +60,7 @@ __device__ __forceinline__ Row<TIn, V> row_load(const TIn* __restrict__ ycol, in
                                                 int64_t n) {
   Row<TIn, V> r;
   r.ok = (uint32_t)s < (uint32_t)nt;
-  r.raw = cl_load<TIn, V>(ycol + (int64_t)(r.ok ? s : 0) * n);
+  r.raw = load_pack<TIn, V, true>(ycol + (int64_t)(r.ok ? s : 0) * n);
   return r;
 }
 
@@ -200,7 +159,7 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
         }
       });
     }
-    CPack<TIn, V> o;
+    Pack<TIn, V> o;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       if constexpr (sizeof(TIn) == 8) {
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
         o.v[k] = is_nan(res[k]) ? canonical_nan_f32() : (float)res[k];  // the one rounding
       }
     }
-    cl_store<TIn, V>(out + g * n + i, o);
+    store_pack<TIn, V, false>(out + g * n + i, o);
   }
 }
 
@@ -218,9 +177,6 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
 // ------------------------------------------------------------------------------------------
 using detail::fail;
 using detail::hip_status;
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b != 0); }
 
 constexpr int64_t kMaxCells = (int64_t)1 << 38;
 constexpr int64_t kMaxSteps = (int64_t)1 << 31;
@@ -262,8 +218,7 @@ int mlx_clim_group_stat(const void* y, int dtype, const int32_t* steps, const in
                         void* stream) {
   if (!y || !steps || !offsets || !out)
     return fail(MLX_E_NULL, "y, steps, offsets, out must not be NULL");
-  if (dtype != MLX_DTYPE_F64 && dtype != MLX_DTYPE_F32)
-    return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
+  if (!is_float_dtype(dtype)) return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
   if (stat < MLX_STAT_MEAN || stat > MLX_STAT_MAX) return fail(MLX_E_ENUM, "unknown MLX_STAT_* stat");
   int64_t total, rows;
   if (nt <= 0 || n <= 0 || nsel <= 0 || ngroups <= 0 || nt >= kMaxSteps || nsel >= kMaxSteps ||
@@ -272,7 +227,7 @@ int mlx_clim_group_stat(const void* y, int dtype, const int32_t* steps, const in
       ceil_div(n, kClimBlock) > 2147483647LL)
     return fail(MLX_E_SHAPE,
                 "need 0 < nt, nsel < 2^31, ngroups > 0, 0 < n <= 2^38, nt*n and ngroups*n addressable");
-  const size_t elem = dtype == MLX_DTYPE_F64 ? 8 : 4;
+  const size_t elem = dtype_size(dtype);
   if (!aligned(y, elem) || !aligned(out, elem)) return fail(MLX_E_ALIGN, "y / out not element-aligned");
   if (!aligned(steps, 4) || !aligned(offsets, 8))
     return fail(MLX_E_ALIGN, "steps not 4-byte or offsets not 8-byte aligned");

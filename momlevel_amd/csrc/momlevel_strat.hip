@@ -30,6 +30,7 @@
 #include "../../include/momlevel_hip.h"
 #include "eos_device.hpp"
 #include "mlx_internal.hpp"
+#include "mlx_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -51,29 +52,6 @@ struct StratArgs {
   double* out;
 };
 
-template <typename TIn, int V>
-struct Pack {
-  TIn v[V];
-};
-
-template <typename TIn, int V>
-__device__ __forceinline__ Pack<TIn, V> load_pack(const TIn* ptr) {
-  Pack<TIn, V> r;
-  if constexpr (V * sizeof(TIn) == 16) {
-    typedef __attribute__((ext_vector_type(4))) unsigned int u4;
-    const u4 raw = __builtin_nontemporal_load(reinterpret_cast<const u4*>(ptr));
-    __builtin_memcpy(r.v, &raw, 16);
-  } else if constexpr (V * sizeof(TIn) == 8 && V > 1) {
-    typedef __attribute__((ext_vector_type(2))) unsigned int u2;
-    const u2 raw = __builtin_nontemporal_load(reinterpret_cast<const u2*>(ptr));
-    __builtin_memcpy(r.v, &raw, 8);
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) r.v[i] = ptr[i];
-  }
-  return r;
-}
-
 // numpy.gradient, one output value.  MODE kF32Faithful: the float32 field meets float64
 // coefficients (the products and sums are float64) and the result is STORED as float32 -- the
 // derivative of a float32 array is a float32 array -- before alpha / beta (float64) see it.
@@ -94,6 +72,7 @@ __device__ __forceinline__ double gradient(TIn f0, TIn f1, TIn f2, double a, dou
 // maze of branches around four copies of the arithmetic.
 template <typename TIn, int V, int MODE, int EOS, int FUNC>
 __global__ __launch_bounds__(kStratBlock) void k_stratification(StratArgs g) {
+  constexpr bool NT = V > 1;  // touched once: `nt`; the one-cell fallback keeps plain element accesses
   const int64_t cell0 = ((int64_t)blockIdx.x * kStratBlock + threadIdx.x) * V;
   if (cell0 >= g.plane) return;
   const int64_t t = blockIdx.y;
@@ -106,8 +85,8 @@ __global__ __launch_bounds__(kStratBlock) void k_stratification(StratArgs g) {
   Pack<TIn, V> tw[3], sw[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    tw[k] = load_pack<TIn, V>(T + k * plane);
-    sw[k] = load_pack<TIn, V>(S + k * plane);
+    tw[k] = load_pack<TIn, V, NT>(T + k * plane);
+    sw[k] = load_pack<TIn, V, NT>(S + k * plane);
   }
 
   // level k from the window: `centre` is the window slot that holds level k itself (a
@@ -115,7 +94,7 @@ __global__ __launch_bounds__(kStratBlock) void k_stratification(StratArgs g) {
   auto emit = [&](int64_t k, auto centre_c, bool central) {
     constexpr int centre = decltype(centre_c)::value;
     const double a = g.coef[3 * k], b = g.coef[3 * k + 1], c = g.coef[3 * k + 2];
-    double res[V];
+    Pack<double, V> res;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const TIn Tc = tw[centre].v[v], Sc = sw[centre].v[v];
@@ -127,25 +106,14 @@ __global__ __launch_bounds__(kStratBlock) void k_stratification(StratArgs g) {
       const double dsdz =
           gradient<MODE, TIn>(sw[0].v[v], sw[1].v[v], sw[2].v[v], a, b, c, central, g.two_dx);
       if constexpr (FUNC == MLX_STRAT_N2) {
-        res[v] = g.gravity * ((alpha * dtdz) - (beta * dsdz));  // derived.py:401
+        res.v[v] = g.gravity * ((alpha * dtdz) - (beta * dsdz));  // derived.py:401
       } else {
         const double r = (beta * dsdz) / (alpha * dtdz);  // derived.py:756
         // np.degrees(np.arctan((1 + R) / (1 - R))): rad2deg multiplies by 180 / pi
-        res[v] = atan((1.0 + r) / (1.0 - r)) * (180.0 / 3.14159265358979323846);
+        res.v[v] = atan((1.0 + r) / (1.0 - r)) * (180.0 / 3.14159265358979323846);
       }
     }
-    double* o = out + k * plane;
-    if constexpr (V == 2) {
-      typedef __attribute__((ext_vector_type(2))) double d2;
-      __builtin_nontemporal_store(d2{res[0], res[1]}, reinterpret_cast<d2*>(o));
-    } else if constexpr (V == 4) {
-      typedef __attribute__((ext_vector_type(2))) double d2;
-      __builtin_nontemporal_store(d2{res[0], res[1]}, reinterpret_cast<d2*>(o));
-      __builtin_nontemporal_store(d2{res[2], res[3]}, reinterpret_cast<d2*>(o + 2));
-    } else {
-#pragma unroll
-      for (int v = 0; v < V; ++v) o[v] = res[v];
-    }
+    store_pack<double, V, NT>(out + k * plane, res);
   };
 
   const bool central = g.uniform != 0;
@@ -154,8 +122,8 @@ __global__ __launch_bounds__(kStratBlock) void k_stratification(StratArgs g) {
   emit(1, integral_constant<int, 1>{}, central);  // interior, window (0, 1, 2)
   for (int64_t k = 2; k < nz - 1; ++k) {
     tw[0] = tw[1], tw[1] = tw[2], sw[0] = sw[1], sw[1] = sw[2];
-    tw[2] = load_pack<TIn, V>(T + (k + 1) * plane);
-    sw[2] = load_pack<TIn, V>(S + (k + 1) * plane);
+    tw[2] = load_pack<TIn, V, NT>(T + (k + 1) * plane);
+    sw[2] = load_pack<TIn, V, NT>(S + (k + 1) * plane);
     emit(k, integral_constant<int, 1>{}, central);
   }
   emit(nz - 1, integral_constant<int, 2>{}, false);  // out[-1] = a f[-3] + b f[-2] + c f[-1]
@@ -210,6 +178,7 @@ __global__ __launch_bounds__(kStratBlock) void k_adjust_n2(const double* n2, int
                                                            int64_t plane, int64_t lead0_rows,
                                                            const double* dz, double* adjusted,
                                                            double* speed) {
+  constexpr bool NT = V > 1;  // touched once: `nt`; the one-cell fallback keeps plain element accesses
   const int64_t cell = ((int64_t)blockIdx.x * kStratBlock + threadIdx.x) * V;
   if (cell >= plane) return;
   const int64_t t = blockIdx.y;
@@ -223,15 +192,15 @@ __global__ __launch_bounds__(kStratBlock) void k_adjust_n2(const double* n2, int
 #pragma unroll
     for (int j = 0; j < kAdjustDepth; ++j)
       if (k0 + j < nz) {
-        x[j] = load_pack<double, V>(col + (k0 + j) * plane);
-        if (speed) w[j] = load_pack<double, V>(dz + (k0 + j) * plane + cell);
+        x[j] = load_pack<double, V, NT>(col + (k0 + j) * plane);
+        if (speed) w[j] = load_pack<double, V, NT>(dz + (k0 + j) * plane + cell);
       }
 #pragma unroll
     for (int j = 0; j < kAdjustDepth; ++j) {
       const int64_t k = k0 + j;
       if (k >= nz) break;
       const bool lead0 = lead0_rows ? (t < lead0_rows) : (k == 0);
-      double m[V];
+      Pack<double, V> m;
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         const double xv = x[j].v[v];
@@ -240,25 +209,15 @@ __global__ __launch_bounds__(kStratBlock) void k_adjust_n2(const double* n2, int
         if (lead0 && a != a) a = 1.0e-8;
         if (a != a) a = carried[v];  // ffill(zcoord)
         carried[v] = a;
-        m[v] = (xv != xv) ? nan : a;  // adjusted * mask
+        m.v[v] = (xv != xv) ? nan : a;  // adjusted * mask
         if (speed) {
-          const double term = sqrt(m[v]) * w[j].v[v];
+          const double term = sqrt(m.v[v]) * w[j].v[v];
           if (term == term) sum[v] += term;  // skipna sum, ascending z as numpy's axis reduce
         }
       }
-      if (adjusted) {
-        double* o = adjusted + (t * nz + k) * plane + cell;
-        if constexpr (V == 2) {
-          typedef __attribute__((ext_vector_type(2))) double d2;
-#if MLX_TUNE_ADJUST_NT_STORE
-          __builtin_nontemporal_store(d2{m[0], m[1]}, reinterpret_cast<d2*>(o));
-#else
-          *reinterpret_cast<d2*>(o) = d2{m[0], m[1]};
-#endif
-        } else {
-          o[0] = m[0];
-        }
-      }
+      if (adjusted)
+        store_pack<double, V, (NT && MLX_TUNE_ADJUST_NT_STORE)>(
+            adjusted + (t * nz + k) * plane + cell, m);
     }
   }
   if (speed) {
