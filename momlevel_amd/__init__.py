@@ -6,7 +6,8 @@ and ``derived.calc_rho`` / ``calc_masso`` / ``calc_volo``, the per-cell trend,
 detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
-include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h).
+include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
+include/momlevel_area.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -23,6 +24,10 @@ reference's C-grid group: relative and potential vorticity as horizontal stencil
 staggered grid, one pass each, consuming the N^2 of ``calc_n2`` and the wave speed of
 ``calc_wave_speed`` where they were computed.
 
+``regional.area_mean`` / ``regional.area_anomaly`` (an EXTENSION: momlevel has no such function)
+reduce a ``(..., yh, xh)`` record to its area-weighted global or per-basin means and to the
+anomalies from them -- the first thing done with a local steric field -- where the record lives.
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -35,6 +40,7 @@ from . import derived
 from . import dynamic
 from . import eos
 from . import reference
+from . import regional
 from . import spice
 from . import staggered_data
 from . import test_data
@@ -64,6 +70,7 @@ __all__ = [
     "eos",
     "halosteric",
     "reference",
+    "regional",
     "spice",
     "steric",
     "steric_variants",

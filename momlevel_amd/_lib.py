@@ -43,6 +43,9 @@ GAUGE_ROWS = 5
 # ---- constants mirrored from include/momlevel_vort.h -------------------------------
 VORT_UNITS_M, VORT_UNITS_CM = 0, 1
 VORT_TILE_LANES, VORT_TILE_H, VORT_TILE_BANDS = 64, 16, 4
+# ---- constants mirrored from include/momlevel_area.h -------------------------------
+AREA_MAX_SLOTS = 16
+AREA_WINDOW = 32
 
 
 def flag_tchunk(steps):
@@ -178,6 +181,16 @@ VORT_SIGNATURES = {
 }
 
 
+# The area-mean entry points (include/momlevel_area.h): bound by load_area() on first use, for the
+# same reason.
+AREA_SIGNATURES = {
+    "mlx_area_tile": (_i64, [_int]),
+    "mlx_area_mean_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "mlx_area_mean": (_int, [_vp, _int, _vp, _int, _vp, _int, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "mlx_area_anomaly": (_int, [_vp, _int, _vp, _int, _vp, _i64, _i64, _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -239,11 +252,12 @@ _GROUPS = {
     "gauge": (GAUGE_SIGNATURES, "the tide-gauge kernels"),
     "spice": (SPICE_SIGNATURES, "the spiciness kernel"),
     "vort": (VORT_SIGNATURES, "the vorticity kernels"),
+    "area": (AREA_SIGNATURES, "the area-mean kernels"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
-_trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = False
+_trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
 
 
 def _load_group(group):
@@ -275,6 +289,10 @@ def load_spice():
 
 def load_vort():
     return _load_group("vort")
+
+
+def load_area():
+    return _load_group("area")
 
 
 def last_error():

@@ -1181,6 +1181,87 @@ def rossby_radius(c, f, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# area-weighted means over the plane (include/momlevel_area.h; csrc/momlevel_area.hip)
+# ---------------------------------------------------------------------------------------
+AREA_MAX_SLOTS = _lib.AREA_MAX_SLOTS  # regions per launch of area_mean
+AREA_WINDOW = _lib.AREA_WINDOW  # records a block keeps the maps in registers for
+
+
+def area_tile(dtype=torch.float64):
+    """Cells of the plane one block of mlx_area_mean reduces for a record of ``dtype`` (a torch or
+    numpy float32 / float64): the order of summation is a function of this and of the plane."""
+    name = str(dtype).replace("torch.", "")
+    name = name if name in ("float32", "float64") else np.dtype(dtype).name
+    if name not in ("float32", "float64"):
+        raise TypeError(f"records are float32 or float64, not {name}")
+    return int(_lib.load_area().mlx_area_tile(DTYPE_F64 if name == "float64" else DTYPE_F32))
+
+
+def _area_slot(slot, nslots, plane, device):
+    if slot is None:
+        if nslots != 1:
+            raise ValueError("without a slot map there is one region: nslots must be 1")
+        return
+    if not (isinstance(slot, torch.Tensor) and slot.is_cuda and slot.dtype == torch.int32
+            and slot.dim() == 1 and slot.is_contiguous()):
+        raise TypeError("slot must be a contiguous 1-D int32 device tensor")
+    if slot.numel() != plane or slot.device != device:
+        raise ValueError(f"slot must hold {plane} elements on {device}")
+
+
+def area_mean(v, area, slot=None, nslots=1):
+    """Area-weighted NaN-aware means over the plane (mlx_area_mean): ``v`` (nrec, plane) and
+    ``area`` (plane) contiguous device tensors, each float32 or float64 on its own; ``slot`` None
+    (one region of every cell) or a (plane) int32 device tensor of slots 0 .. nslots-1, negative =
+    no region, with ``nslots`` <= AREA_MAX_SLOTS.  Returns ``(mean, den)``, both (nrec, nslots)
+    float64: ``den`` is the valid area under each mean, ``mean`` NaN where it is 0.  Fixed order of
+    summation, no atomics: two runs agree to the bit, and a record's means depend on that record
+    alone."""
+    require_device()
+    lib = _lib.load_area()
+    vdt, adt = _float_code(v, "v", 2), _float_code(area, "area", 1)
+    nrec, plane = (int(n) for n in v.shape)
+    if area.numel() != plane or area.device != v.device:
+        raise ValueError(f"area must hold {plane} elements on {v.device}")
+    nslots = int(nslots)
+    if not 1 <= nslots <= AREA_MAX_SLOTS:
+        raise ValueError(f"nslots must be 1 .. {AREA_MAX_SLOTS}, got {nslots}: launch in groups")
+    _area_slot(slot, nslots, plane, v.device)
+    mean = torch.empty((nrec, nslots), dtype=torch.float64, device=v.device)
+    den = torch.empty((nrec, nslots), dtype=torch.float64, device=v.device)
+    if nrec == 0:
+        return mean, den
+    if plane == 0:  # numpy: the sum of nothing is 0, 0 / 0 is NaN
+        return mean.fill_(float("nan")), den.zero_()
+    nbytes = int(lib.mlx_area_mean_workspace_bytes(nrec, plane, nslots, vdt))
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=v.device)
+    _call(lib, "mlx_area_mean", v.device, _ptr(v), vdt, _ptr(area), adt, _ptr(slot), nslots, nrec,
+          plane, _ptr(mean), _ptr(den), _ptr(ws), nbytes)
+    return mean, den
+
+
+def area_anomaly(v, mean, slot=None, out=None):
+    """``v.astype(float64) - mean[rec, slot]`` (mlx_area_anomaly): ``v`` (nrec, plane) float32 or
+    float64, ``mean`` (nrec, nslots) float64, ``slot`` as in area_mean (any number of slots); cells
+    of no slot give NaN.  Returns (nrec, plane) float64 (``out`` when given)."""
+    require_device()
+    lib = _lib.load_area()
+    vdt = _float_code(v, "v", 2)
+    nrec, plane = (int(n) for n in v.shape)
+    if (_float_code(mean, "mean", 2) != DTYPE_F64 or int(mean.shape[0]) != nrec
+            or mean.device != v.device):
+        raise ValueError(f"mean must be a float64 ({nrec}, nslots) tensor on {v.device}")
+    nslots = int(mean.shape[1])
+    if nslots < 1:
+        raise ValueError("mean must hold at least one slot")
+    _area_slot(slot, nslots, plane, v.device)
+    out = _out_like(out, (nrec, plane), torch.float64, v.device, "float64")
+    _call(lib, "mlx_area_anomaly", v.device, _ptr(v), vdt, _ptr(slot), nslots, _ptr(mean), nrec,
+          plane, _ptr(out))
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

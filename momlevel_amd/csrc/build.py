@@ -26,6 +26,7 @@ FEATURES = {
     "gauge": ["eos_device.hpp", "mlx_internal.hpp", "include/momlevel_gauge.h"],
     "spice": ["mlx_internal.hpp", "include/momlevel_spice.h"],
     "vort": ["mlx_internal.hpp", "include/momlevel_vort.h"],
+    "area": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_area.h"],
 }
 
 
@@ -117,6 +118,11 @@ def spice_source_sha():
 def vort_source_sha():
     """the vorticity kernels' own guard: csrc/momlevel_vort.hip (+ what it includes, + flags)"""
     return feature_source_sha("vort")
+
+
+def area_source_sha():
+    """the area-mean kernels' own guard: csrc/momlevel_area.hip (+ what it includes, + flags)"""
+    return feature_source_sha("area")
 
 
 def hipcc():
