@@ -351,17 +351,37 @@ def _case_fields(shape, dtype, seed=3):
 T32_S64, T64_S32 = (np.float32, np.float64), (np.float64, np.float32)  # fields of different dtypes
 
 
+# Planes past one block of cells (K1 covers 2048 cells a block, 1024 on the scalar twin; K2
+# 256 x 2 or 256 x 4 columns): 2 x 2052 = 4104 cells, rows 16-byte aligned at either dtype -- two K1
+# blocks and 8 cells, 5 to 9 K2 blocks, the last ragged; 3 x 1367 = 4101 cells, odd: the scalar twins
+# over four blocks and 5 cells.  Both have land cells in the ragged tail.
+SEAM_SHAPES = [(9, 3, 2, 2052), (9, 3, 3, 1367)]
+
+
 @pytest.mark.parametrize("skip_dry", [False, True])
 @pytest.mark.parametrize("dtype,f32_mode", [(np.float64, "faithful"), (np.float32, "faithful"),
                                             (np.float32, "upcast"), (T32_S64, "faithful"),
                                             (T64_S32, "faithful"), (T32_S64, "upcast")])
-@pytest.mark.parametrize("shape", [(37, 5, 12, 40), (9, 3, 7, 9), (3, 4, 2, 1024)])
+@pytest.mark.parametrize("shape", [(37, 5, 12, 40), (9, 3, 7, 9), (3, 4, 2, 1024)] + SEAM_SHAPES)
 def test_decomposition_rows_equal_single_variant_launches(shape, dtype, f32_mode, skip_dry):
     """mlx_steric_global_decomp: rows 0-2 bit-identical to three mlx_steric_global calls (same
     tiling, same order), row 3 = sum(theta*vol0) vs numpy; 12x40 / 2x1024 planes take the dwordx4
-    kernel, 7x9 the scalar twin; nt=37 spans two 32-step time chunks.  A pair of dtypes = theta and
+    kernel, 7x9 the scalar twin; nt=37 spans two 32-step time chunks; SEAM_SHAPES cross the blocks
+    of either twin.  A pair of dtypes = theta and
     salinity stored with different precisions (MLX_DTYPE_T32_S64 / _T64_S32: numpy's promotion per
     sub-expression, exact arithmetic whatever the default policy says; "upcast": both widened)."""
+    _decomposition_rows(shape, dtype, f32_mode, skip_dry)
+
+
+@pytest.mark.parametrize("skip_dry", [False, True])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_decomposition_rows_long_record_across_a_block_seam(dtype, skip_dry):
+    """the same assertions on (70, 2, 2, 2052): the 64-step chunk of the held-field passes and a
+    block seam of the plane at once"""
+    _decomposition_rows((70, 2, 2, 2052), dtype, "faithful", skip_dry)
+
+
+def _decomposition_rows(shape, dtype, f32_mode, skip_dry):
     g, T, S = _case_fields(shape, dtype)
     dT, dS = torch.from_numpy(T).cuda(), torch.from_numpy(S).cuda()
     vol0 = torch.from_numpy(g["volcello"]).cuda()
@@ -398,7 +418,7 @@ def test_decomposition_with_a_separate_reference_state():
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-@pytest.mark.parametrize("shape", [(19, 6, 12, 40), (5, 3, 7, 9)])
+@pytest.mark.parametrize("shape", [(19, 6, 12, 40), (5, 3, 7, 9)] + SEAM_SHAPES)
 def test_fused_arithmetic_meets_the_parity_gate(shape, dtype):
     """MLX_FLAG_FMA (opt-in): rho and masso within 1e-10 relative of the oracle (north_star's fp64
     tolerance), delta_rho / eta within 1e-10 * max|ref|; and the fused kernels agree with EACH
@@ -794,7 +814,7 @@ def test_config5_f32_properties():
                                                   (T32_S64, "faithful", "exact"),
                                                   (T64_S32, "faithful", "exact"),
                                                   (T64_S32, "upcast", "exact")])
-@pytest.mark.parametrize("shape", [(19, 5, 12, 40), (9, 3, 7, 9), (5, 4, 6, 10)])
+@pytest.mark.parametrize("shape", [(19, 5, 12, 40), (9, 3, 7, 9), (5, 4, 6, 10)] + SEAM_SHAPES)
 def test_local_decomposition_fields_equal_single_variant_launches(shape, dtype, f32_mode, arith,
                                                                    want_delta_rho):
     """mlx_steric_local_decomp: the three delta_rho / eta fields from ONE pass over theta/S are

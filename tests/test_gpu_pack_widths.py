@@ -12,6 +12,8 @@ held against the numpy restatement of the feature's own GPU test, as that test a
 The time axis is as short as each function allows: 4 steps for the fit, two groups of 3 for the
 statistic, 3 levels for the stratification.  (The spiciness and vorticity kernels have their own:
 test_views_and_prefixes_are_slices_of_the_whole, test_record_slices_offset_pointers_and_two_runs.)
+The same placements over several blocks of cells, with a ragged last block, are in
+test_gpu_trend_edges.py and test_gpu_clim_edges.py.
 """
 
 import numpy as np

@@ -110,12 +110,14 @@ LEVELS = {
 
 @pytest.mark.parametrize("levels", sorted(LEVELS))
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-@pytest.mark.parametrize("shape", [(3, 7, 6, 10), (2, 3, 5, 7), (9, 4, 8), (1, 12, 3, 64)])
+@pytest.mark.parametrize("shape", [(3, 7, 6, 10), (2, 3, 5, 7), (9, 4, 8), (1, 12, 3, 64),
+                                   (2, 5, 1, 513)])
 def test_n2_bit_identical_to_numpy(shape, dtype, levels):
     """Every value of N^2 is numpy's: uneven and even level spacing (numpy.gradient's two
     branches), float64 and float32 fields (a float32 field's derivative is float32, alpha and beta
-    float64), land / sub-bottom NaN, odd planes (the one-cell-per-thread kernel) and 16-byte ones,
-    3-D and 4-D layouts; the adjustment and the wave speed on top."""
+    float64), land / sub-bottom NaN, odd planes (the one-cell-per-thread kernel; 513 cells: over
+    three blocks, the last of one cell) and 16-byte ones, 3-D and 4-D layouts; the adjustment and
+    the wave speed on top."""
     nz = shape[-3]
     z = LEVELS[levels](nz)
     T, S = _fields(shape, dtype, seed=sum(shape) + nz)
@@ -138,6 +140,30 @@ def test_n2_bit_identical_to_numpy(shape, dtype, levels):
         assert_bit_equal(speed.values, o.calc_wave_speed(ref, dz))
     else:
         assert_bit_equal(speed.values, o.calc_wave_speed_4d_quirk(ref, dz))
+
+
+def test_adjustment_and_wave_speed_on_an_odd_plane_of_three_blocks():
+    """adjust_negative_n2 and calc_wave_speed of a given (z, y, x) field on 513 cells: the
+    one-cell-per-thread twin of the adjustment over three blocks, the surface as ``n2[0]``.  The
+    field is drawn, not computed: a third of its values non-positive, land columns, sub-bottom NaN,
+    a NaN surface above valid levels."""
+    shape = (5, 1, 513)
+    r = np.random.default_rng(513)
+    n2 = r.normal(1.0e-5, 2.0e-5, shape)
+    n2[:, :, r.random(513) < 0.2] = np.nan
+    n2[3:, :, r.random(513) < 0.3] = np.nan
+    n2[0, :, r.random(513) < 0.1] = np.nan
+    n2[:, :, 511], n2[0, :, 512], n2[2, :, 512] = np.nan, -1.0e-6, np.nan  # the last cells
+    assert (n2 <= 0.0).any() and np.isnan(n2[:, 0, 511]).all() and not np.isnan(n2[:, 0, 512]).all()
+    dz = np.abs(r.normal(10.0, 3.0, shape))
+    dz[np.isnan(n2)] = np.nan
+    dims = ("z_l", "yh", "xh")
+    ref = o.adjust_negative_n2(n2)
+    assert_bit_equal(derived.adjust_negative_n2(DataArray(n2, dims)).values, ref, "adjust_negative_n2")
+    speed = derived.calc_wave_speed(DataArray(n2, dims), DataArray(dz, dims))
+    want = o.calc_wave_speed(n2, dz)
+    assert speed.dims == ("yh", "xh") and np.isnan(want).any() and not np.isnan(want).all()
+    assert_bit_equal(speed.values, want, "calc_wave_speed")
 
 
 def test_pressure_operands_and_device_inputs():
