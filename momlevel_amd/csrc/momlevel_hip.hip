@@ -43,6 +43,11 @@ constexpr int kNTC = 8;      // time steps whose per-thread partials are parked 
 
 // ------------------------------------------------------------------------------------
 // vector load helpers: VEC elements of TIn = 16 bytes (double2 / float4), or scalar
+//
+// Private copies, not mlx_pack.hpp's: with the header's Pack / load_pack / store_pack 228 of this
+// unit's 473 kernels compile to other code (every fast k_steric_local, the fast k_eos_map, the
+// float32-in / float64-out probes: another register assignment and schedule, 72 K2 kernels on
+// another VGPR count), which only timings on the GPU can accept.
 // ------------------------------------------------------------------------------------
 template <typename TIn, int VEC>
 struct Pack {
@@ -803,17 +808,13 @@ __device__ __forceinline__ double dz_default(double depth, double ztop, double z
 // 16 B read + 3*8 B written per cell instead of 3 x (16 or 8 read + 8 written).  Each field is
 // bit-identical to its single-variant launch (same arithmetic tree, z ascending).
 // P3D (fast kernels): the pressure is a (z,y,x) field, read per level like rho0m (see K1).
-// LDSACC (round 5 experiment, -DMLX_TUNE_K2_LDSACC=1; off in the product): the column sums of the
-// NTI time steps live in LDS ([step][column][thread]: a wave's 64 lanes hit 64 consecutive doubles,
-// conflict-free; every thread owns its slots, no barrier) instead of VGPRs, so that one thread can
-// take 32 steps of one column -- north_star's "LDS-staged z-column tiles", VERDICT r4 next #5.
 // DRHO32 (MLX_FLAG_DRHO_F32): delta_rho_out holds FLOAT32 elements.  Each value is narrowed in
 // registers (v_cvt_f32_f64, round to nearest even: numpy's astype(float32)) right before its
 // non-temporal store -- 4 B/cell written instead of 8 -- AFTER dz * delta_rho has been taken from the
 // float64 value: the column sums, and with them eta, are bit for bit those of the float64 launch.
 // drho_vstride and the per-step offset count elements of the output type.
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GENERIC, bool SKIP, bool FMA,
-          bool P3D = false, bool LDSACC = false, bool DRHO32 = false>
+          bool P3D = false, bool DRHO32 = false>
 __global__ __launch_bounds__(kBlock) void k_steric_local(
     const TIn* __restrict__ T, const TIn* __restrict__ S, const TIn* __restrict__ T0,
     const TIn* __restrict__ S0, const double* __restrict__ rho0m,
@@ -823,7 +824,6 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
     int64_t plane, int64_t t_stride_T, int64_t t_stride_S,
     typename std::conditional<DRHO32, float, double>::type* __restrict__ drho_out,
     int64_t drho_vstride, double* __restrict__ eta_out, int64_t eta_vstride, int ntb_major) {
-  static_assert(!(DRHO32 && LDSACC), "the LDS column-sum experiment is eta-only");
   constexpr int NOUT = (VAR == kVarAll) ? 3 : 1;
   constexpr bool STREAM_T = (VAR != kVarHalo), STREAM_S = (VAR != kVarThermo);
   constexpr bool HELD_T = (VAR == kVarHalo || VAR == kVarAll);
@@ -860,20 +860,13 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
   const int t0 = tb * NTI;
   const int64_t n3 = (int64_t)nz * plane;
 
-  constexpr int NREG = LDSACC ? 1 : NTI;  // (LDSACC: the register array shrinks to a placeholder)
-  double acc[NOUT][NREG][VEC];
-  __shared__ double sacc[LDSACC ? NTI * VEC * kBlock : 1];
-  static_assert(!LDSACC || NOUT == 1, "LDS column sums: single-variant passes only");
+  double acc[NOUT][NTI][VEC];
 #pragma unroll
   for (int o = 0; o < NOUT; ++o)
 #pragma unroll
-    for (int j = 0; j < NREG; ++j)
+    for (int j = 0; j < NTI; ++j)
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[o][j][k] = 0.0;
-  if constexpr (LDSACC) {
-#pragma unroll
-    for (int i = 0; i < NTI * VEC; ++i) sacc[i * kBlock + threadIdx.x] = 0.0;
-  }
 
   Pack<double, VEC> depth;
   if (dz == nullptr) depth = load_pack<double, VEC>(deptho + col);
@@ -1019,13 +1012,7 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
         auto cell = [&](int o, int k) -> double {
           const double dr = rho[o][k] - r0.v[k];
           const double term = dzv.v[k] * dr;
-          if constexpr (LDSACC) {
-            double c = sacc[(j * VEC + k) * kBlock + threadIdx.x];
-            add_skipna<PRED>(c, term);
-            sacc[(j * VEC + k) * kBlock + threadIdx.x] = c;
-          } else {
-            add_skipna<PRED>(acc[o][j][k], term);  // skipna, z ascending like numpy
-          }
+          add_skipna<PRED>(acc[o][j][k], term);  // skipna, z ascending like numpy
           return dr;
         };
         if constexpr (DRHO32) {
@@ -1071,8 +1058,7 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
         Pack<double, VEC> e;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          const double sum = LDSACC ? sacc[(j * VEC + k) * kBlock + threadIdx.x] : acc[o][LDSACC ? 0 : j][k];
-          e.v[k] = is_nan(surf.v[k]) ? canonical_nan() : neg_inv_rhozero * sum;
+          e.v[k] = is_nan(surf.v[k]) ? canonical_nan() : neg_inv_rhozero * acc[o][j][k];
         }
         store_pack<VEC>(eta_out + o * eta_vstride + (int64_t)(t0 + j) * plane + col, e);
       }
@@ -1253,9 +1239,6 @@ constexpr int kNTIGen = 8;           // generic scalar path
 #ifndef MLX_TUNE_K2_TBMAJOR
 #define MLX_TUNE_K2_TBMAJOR 1
 #endif
-#ifndef MLX_TUNE_K2_LDSACC
-#define MLX_TUNE_K2_LDSACC 0
-#endif
 // float32 fields: FOUR columns per thread (one 16-byte load per field, level and step) only for the
 // steric pass without delta_rho; every other pass runs TWO (8-byte loads): half the registers per
 // step buy twice the steps in flight at the same occupancy -- held-field passes 7-8 % faster without
@@ -1370,92 +1353,97 @@ bool fast_layout(int dtype, int p_mode, int eos, int64_t plane, int64_t sT, int6
   return true;
 }
 
+// The run-time dtype as the compile-time pair of every kernel here: f(TIn{}, MODE constant), TIn the
+// element type the kernel is instantiated on (theta / S of different dtypes run the float64 shape and
+// read their float32 field through load_field).  The one place that spells the mapping out.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <typename F>
+auto with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case MLX_DTYPE_F64: return f(double{}, Int<kF64>{});
+    case MLX_DTYPE_F32: return f(float{}, Int<kF32Faithful>{});
+    case MLX_DTYPE_T32_S64: return f(double{}, Int<kMixT32>{});
+    case MLX_DTYPE_T64_S32: return f(double{}, Int<kMixS32>{});
+    default: return f(float{}, Int<kF32Upcast>{});
+  }
+}
+
 // ---- K1 dispatch -------------------------------------------------------------------------
 struct K1Args {
-  dim3 grid;
   hipStream_t st;
   const void *T, *S, *T0, *S0;
   const double *vol0, *p;
-  int p_mode, eos, nt, t_chunk;
+  int p_mode, eos, nt, nz, t_chunk;
   int64_t plane, sT, sS;
   double* partials;
-  int64_t nblk;
+  int64_t nblk;  // out: partials per row, set by the launcher whose tiling decides it
   bool p3d;  // fast kernels: the pressure is a (z,y,x) field (template argument P3D)
 };
 
+// The launcher owns the grid: the cells of a z level one block covers follow from ITS VEC and U.
 template <typename TIn, int VEC, int U, int VAR, int MODE, bool GEN, bool SKIP, bool FMA,
           bool P3D>
-void k1_launch(const K1Args& a) {
+int k1_launch(K1Args& a) {
+  const int64_t gx = ceil_div(a.plane, (int64_t)kBlock * VEC * U), ntc = ceil_div(a.nt, a.t_chunk);
+  if (ntc > 65535) return fail(MLX_E_SHAPE, "nt too large for one call: chunk it");
+  if (gx > 2147483647LL) return fail(MLX_E_SHAPE, "plane too large");
+  a.nblk = gx * a.nz;
   snprintf(g_kernel, sizeof(g_kernel), "k_steric_global<%s,%d,%d,%d,%d,%s,%s,%s%s>",
            type_name<TIn>(), VEC, U, VAR, MODE, tf(GEN), tf(SKIP), tf(FMA), P3D ? ",true" : "");
-  hipLaunchKernelGGL((k_steric_global<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, P3D>), a.grid,
-                     dim3(kBlock), 0, a.st, (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0,
-                     (const TIn*)a.S0, a.vol0, a.p, a.p_mode, a.eos, a.nt, a.t_chunk, a.plane,
-                     a.sT, a.sS, a.partials, a.nblk);
+  hipLaunchKernelGGL((k_steric_global<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, P3D>),
+                     dim3((unsigned)gx, (unsigned)a.nz, (unsigned)ntc), dim3(kBlock), 0, a.st,
+                     (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0, (const TIn*)a.S0, a.vol0,
+                     a.p, a.p_mode, a.eos, a.nt, a.t_chunk, a.plane, a.sT, a.sS, a.partials, a.nblk);
+  return 0;
 }
 
 template <typename TIn, int VEC, int U, int VAR, int MODE, bool GEN, bool SKIP, bool FMA>
-void k1_go(const K1Args& a) {
+int k1_go(K1Args& a) {
   if constexpr (!GEN && VAR != kVarAll) {
-    if (a.p3d) {
-      k1_launch<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, true>(a);
-      return;
-    }
+    if (a.p3d) return k1_launch<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, true>(a);
   }
-  k1_launch<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, false>(a);
+  return k1_launch<TIn, VEC, U, VAR, MODE, GEN, SKIP, FMA, false>(a);
 }
 
 template <typename TIn, int VEC, int U, int VAR, int MODE, bool GEN>
-void k1_flags(const K1Args& a, bool skip, bool fma) {
-  constexpr int FM = MODE;   // (faithful float32 keeps its float32 polynomial under MLX_FLAG_FMA)
+int k1_flags(K1Args& a, bool skip, bool fma) {
   constexpr bool S1 = !GEN;  // the generic twin has no skipping instantiation
-  if constexpr (IsMixed<MODE>::value) {  // exact arithmetic only (the entry points refuse the flag)
-    if (skip && S1) k1_go<TIn, VEC, U, VAR, MODE, GEN, S1, false>(a);
-    else k1_go<TIn, VEC, U, VAR, MODE, GEN, false, false>(a);
-  } else if (fma) {
-    if (skip && S1) k1_go<TIn, VEC, U, VAR, FM, GEN, S1, true>(a);
-    else k1_go<TIn, VEC, U, VAR, FM, GEN, false, true>(a);
-  } else {
-    if (skip && S1) k1_go<TIn, VEC, U, VAR, MODE, GEN, S1, false>(a);
-    else k1_go<TIn, VEC, U, VAR, MODE, GEN, false, false>(a);
+  // theta / S of different dtypes: exact arithmetic only (the entry points refuse the flag).
+  // (faithful float32 keeps its float32 polynomial under MLX_FLAG_FMA)
+  if constexpr (!IsMixed<MODE>::value) {
+    if (fma)
+      return (skip && S1) ? k1_go<TIn, VEC, U, VAR, MODE, GEN, S1, true>(a)
+                          : k1_go<TIn, VEC, U, VAR, MODE, GEN, false, true>(a);
   }
+  return (skip && S1) ? k1_go<TIn, VEC, U, VAR, MODE, GEN, S1, false>(a)
+                      : k1_go<TIn, VEC, U, VAR, MODE, GEN, false, false>(a);
 }
 
 template <typename TIn, int VEC, int U, int MODE, bool GEN>
-void k1_var(const K1Args& a, int var, bool skip, bool fma) {
+int k1_var(K1Args& a, int var, bool skip, bool fma) {
   if constexpr (GEN) {  // held fields reach the generic twin as stride-0 streams (VAR 0)
-    if (var == kVarAll) k1_flags<TIn, VEC, U, kVarAll, MODE, GEN>(a, skip, fma);
-    else k1_flags<TIn, VEC, U, kVarSteric, MODE, GEN>(a, skip, fma);
+    if (var == kVarAll) return k1_flags<TIn, VEC, U, kVarAll, MODE, GEN>(a, skip, fma);
+    return k1_flags<TIn, VEC, U, kVarSteric, MODE, GEN>(a, skip, fma);
   } else {
     switch (var) {
-      case kVarSteric: k1_flags<TIn, VEC, U, kVarSteric, MODE, GEN>(a, skip, fma); break;
-      case kVarHalo: k1_flags<TIn, VEC, U, kVarHalo, MODE, GEN>(a, skip, fma); break;
-      case kVarThermo: k1_flags<TIn, VEC, U, kVarThermo, MODE, GEN>(a, skip, fma); break;
-      default: k1_flags<TIn, VEC, U, kVarAll, MODE, GEN>(a, skip, fma); break;
+      case kVarSteric: return k1_flags<TIn, VEC, U, kVarSteric, MODE, GEN>(a, skip, fma);
+      case kVarHalo: return k1_flags<TIn, VEC, U, kVarHalo, MODE, GEN>(a, skip, fma);
+      case kVarThermo: return k1_flags<TIn, VEC, U, kVarThermo, MODE, GEN>(a, skip, fma);
+      default: return k1_flags<TIn, VEC, U, kVarAll, MODE, GEN>(a, skip, fma);
     }
   }
 }
 
-void k1_dispatch(const K1Args& a, int dtype, bool fast, int var, bool skip, bool fma) {
-  if (fast) {
-    if (dtype == MLX_DTYPE_F64) k1_var<double, kVec64, kU64, kF64, false>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_F32) k1_var<float, kVec32, kU32, kF32Faithful, false>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T32_S64) k1_var<double, kVec64, kU64, kMixT32, false>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T64_S32) k1_var<double, kVec64, kU64, kMixS32, false>(a, var, skip, fma);
-    else k1_var<float, kVec32, kU32, kF32Upcast, false>(a, var, skip, fma);
-  } else {
-    if (dtype == MLX_DTYPE_F64) k1_var<double, 1, kUGen, kF64, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_F32) k1_var<float, 1, kUGen, kF32Faithful, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T32_S64) k1_var<double, 1, kUGen, kMixT32, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T64_S32) k1_var<double, 1, kUGen, kMixS32, true>(a, var, skip, fma);
-    else k1_var<float, 1, kUGen, kF32Upcast, true>(a, var, skip, fma);
-  }
-}
-
-int64_t k1_blocks(bool fast, int dtype, int64_t plane) {
-  const int64_t cells = fast ? (int64_t)kBlock * 8 : (int64_t)kBlock * kUGen;
-  (void)dtype;  // 8 cells per thread for both fast dtypes
-  return ceil_div(plane, cells);
+int k1_dispatch(K1Args& a, int dtype, bool fast, int var, bool skip, bool fma) {
+  return with_dtype(dtype, [&](auto tin, auto mode) {
+    using TIn = decltype(tin);
+    constexpr int MODE = decltype(mode)::value;
+    constexpr bool F64 = sizeof(TIn) == 8;
+    if (fast)
+      return k1_var<TIn, F64 ? kVec64 : kVec32, F64 ? kU64 : kU32, MODE, false>(a, var, skip, fma);
+    return k1_var<TIn, 1, kUGen, MODE, true>(a, var, skip, fma);
+  });
 }
 
 int k1_time_chunk(int flags, int64_t nt, int var) {
@@ -1498,18 +1486,14 @@ int steric_global_impl(const void* T, const void* S, const void* T0, const void*
   }
   K1Args a;
   a.p3d = fast && p_mode == MLX_P_FULL3D;
-  const int64_t gx = k1_blocks(fast, dtype, plane);
   a.t_chunk = k1_time_chunk(flags, nt, var);
-  if (ceil_div(nt, a.t_chunk) > 65535) return fail(MLX_E_SHAPE, "nt too large for one call: chunk it");
-  if (gx > 2147483647LL) return fail(MLX_E_SHAPE, "plane too large");
-  a.grid = dim3((unsigned)gx, (unsigned)nz, (unsigned)ceil_div(nt, a.t_chunk));
   a.st = (hipStream_t)stream;
   a.T = T; a.S = S; a.T0 = T0 ? T0 : T; a.S0 = S0 ? S0 : S;
   a.vol0 = vol0; a.p = p ? p : vol0;  // p is never dereferenced for the linear EOS
-  a.p_mode = p_mode; a.eos = eos; a.nt = (int)nt;
+  a.p_mode = p_mode; a.eos = eos; a.nt = (int)nt; a.nz = (int)nz;
   a.plane = plane; a.sT = sT; a.sS = sS;
-  a.partials = (double*)workspace; a.nblk = gx * nz;
-  k1_dispatch(a, dtype, fast, var, skip, fma);
+  a.partials = (double*)workspace;
+  if (int rc = k1_dispatch(a, dtype, fast, var, skip, fma)) return rc;  // (a shape refusal)
   if (int rc = hip_status(hipGetLastError(), name)) return rc;
   hipLaunchKernelGGL(k_reduce_rows, dim3((unsigned)(nout * nt)), dim3(kBlock), 0, a.st,
                      a.partials, a.nblk, out);
@@ -1518,7 +1502,6 @@ int steric_global_impl(const void* T, const void* S, const void* T0, const void*
 
 // ---- K2 dispatch -------------------------------------------------------------------------
 struct K2Args {
-  dim3 grid;
   hipStream_t st;
   const void *T, *S, *T0, *S0;
   const double *rho0m, *surf, *dz, *z_i, *deptho, *p;
@@ -1530,24 +1513,38 @@ struct K2Args {
   int64_t drho_vstride, eta_vstride;
   bool drho32;
   bool p3d;  // fast kernels: the pressure is a (z,y,x) field (template argument P3D)
-  int ntb_major;  // > 0: 1-D grid, a tile's time blocks adjacent on one XCD (k_steric_local)
 };
 
+// The launcher owns the grid: which columns and time steps a thread takes are ITS VEC and NTI, so
+// the blocks that cover the plane and the record are counted here and nowhere else.
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA,
-          bool P3D, bool LDSACC = false, bool DRHO32 = false>
-void k2_launch(const K2Args& a) {
+          bool P3D, bool DRHO32 = false>
+int k2_launch(const K2Args& a) {
   typedef typename std::conditional<DRHO32, float, double>::type TOut;
+  const int64_t gx = ceil_div(a.plane, (int64_t)kBlock * VEC), ntb = ceil_div(a.nt, NTI);
+  if (ntb > 65535) return fail(MLX_E_SHAPE, "nt too large for one call: chunk it");
+  if (gx > 2147483647LL) return fail(MLX_E_SHAPE, "plane too large");
+  dim3 grid((unsigned)gx, (unsigned)ntb);
+  int ntb_major = 0;  // > 0: 1-D grid, a tile's time blocks adjacent on one XCD (k_steric_local)
+  // time blocks of a tile side by side on one XCD (see the kernel) when there is more than one
+  // (a HIP grid holds fewer than 2^32 THREADS: beyond 2^24 - 1 blocks of kBlock the 1-D form
+  //  would not launch where the (tiles, time blocks) grid does -- ADVICE r5)
+  const int64_t blocks = ceil_div(gx, 8) * 8 * ntb;
+  if (MLX_TUNE_K2_TBMAJOR && ntb > 1 && blocks <= kK2MaxBlocks1D) {
+    grid = dim3((unsigned)blocks);
+    ntb_major = (int)ntb;
+  }
   // (a float32-egress instantiation carries a trailing ",f32out": a profile row of it cannot be
   //  taken for the float64 one)
-  snprintf(g_kernel, sizeof(g_kernel), "k_steric_local<%s,%d,%d,%d,%d,%s,%s,%s%s%s%s>",
-           type_name<TIn>(), VEC, NTI, VAR, MODE, tf(GEN), tf(SKIP), tf(FMA),
-           (P3D || LDSACC) ? (P3D ? ",true" : ",false") : "", LDSACC ? ",lds" : "",
+  snprintf(g_kernel, sizeof(g_kernel), "k_steric_local<%s,%d,%d,%d,%d,%s,%s,%s%s%s>",
+           type_name<TIn>(), VEC, NTI, VAR, MODE, tf(GEN), tf(SKIP), tf(FMA), P3D ? ",true" : "",
            DRHO32 ? ",f32out" : "");
   hipLaunchKernelGGL(
-      (k_steric_local<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, LDSACC, DRHO32>), a.grid,
-      dim3(kBlock), 0, a.st, (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0, (const TIn*)a.S0,
-      a.rho0m, a.surf, a.dz, a.z_i, a.deptho, a.p, a.p_mode, a.eos, a.neg_inv_rhozero, a.nt, a.nz,
-      a.plane, a.sT, a.sS, (TOut*)a.drho, a.drho_vstride, a.eta, a.eta_vstride, a.ntb_major);
+      (k_steric_local<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, DRHO32>), grid, dim3(kBlock), 0,
+      a.st, (const TIn*)a.T, (const TIn*)a.S, (const TIn*)a.T0, (const TIn*)a.S0, a.rho0m, a.surf,
+      a.dz, a.z_i, a.deptho, a.p, a.p_mode, a.eos, a.neg_inv_rhozero, a.nt, a.nz, a.plane, a.sT,
+      a.sS, (TOut*)a.drho, a.drho_vstride, a.eta, a.eta_vstride, ntb_major);
+  return 0;
 }
 
 // DR: which delta_rho egress this shape is launched with.  kDrBoth: float64 or float32 (the generic
@@ -1557,65 +1554,50 @@ void k2_launch(const K2Args& a) {
 constexpr int kDrF64 = 0, kDrBoth = 1, kDrF32 = 2;
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA, bool P3D,
           int DR>
-void k2_out(const K2Args& a) {
+int k2_out(const K2Args& a) {
   if constexpr (DR != kDrF64) {
-    if (DR == kDrF32 || (a.drho32 && a.drho != nullptr)) {
-      k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, false, true>(a);
-      return;
-    }
+    if (DR == kDrF32 || (a.drho32 && a.drho != nullptr))
+      return k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D, true>(a);
   }
-  if constexpr (DR != kDrF32) k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D>(a);
+  if constexpr (DR != kDrF32) return k2_launch<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, P3D>(a);
+  return 0;  // (not reached: DR == kDrF32 returned above)
 }
 
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, bool SKIP, bool FMA,
           int DR = kDrBoth>
-void k2_go(const K2Args& a) {
+int k2_go(const K2Args& a) {
   if constexpr (!GEN && VAR != kVarAll) {
-    if (a.p3d) {
-      k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, true, DR>(a);
-      return;
-    }
+    if (a.p3d) return k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, true, DR>(a);
   }
-  k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, false, DR>(a);
+  return k2_out<TIn, VEC, NTI, VAR, MODE, GEN, SKIP, FMA, false, DR>(a);
 }
 
 template <typename TIn, int VEC, int NTI, int VAR, int MODE, bool GEN, int DR = kDrBoth>
-void k2_flags(const K2Args& a, bool skip, bool fma) {
-  constexpr int FM = MODE;
-  constexpr bool S1 = !GEN;
-  if constexpr (IsMixed<MODE>::value) {  // exact arithmetic only
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false, DR>(a);
-    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false, DR>(a);
-  } else if (fma) {
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, FM, GEN, S1, true, DR>(a);
-    else k2_go<TIn, VEC, NTI, VAR, FM, GEN, false, true, DR>(a);
-  } else {
-    if (skip && S1) k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false, DR>(a);
-    else k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false, DR>(a);
+int k2_flags(const K2Args& a, bool skip, bool fma) {
+  constexpr bool S1 = !GEN;  // the generic twin has no skipping instantiation
+  if constexpr (!IsMixed<MODE>::value) {  // (theta / S of different dtypes: exact arithmetic only)
+    if (fma)
+      return (skip && S1) ? k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, true, DR>(a)
+                          : k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, true, DR>(a);
   }
+  return (skip && S1) ? k2_go<TIn, VEC, NTI, VAR, MODE, GEN, S1, false, DR>(a)
+                      : k2_go<TIn, VEC, NTI, VAR, MODE, GEN, false, false, DR>(a);
 }
 
 // a single-variant fast kernel with the time steps per thread of its instantiation (k2_nti)
 template <typename TIn, int VEC, int VAR, int MODE>
-void k2_single(const K2Args& a, bool skip, bool fma) {
+int k2_single(const K2Args& a, bool skip, bool fma) {
   constexpr bool F64 = sizeof(TIn) == 8;
   // (the columns per thread are the instantiation's too: k2_vec32, k2_vec64; theta / S of different
   // dtypes keep the two columns of their float64 shape)
   constexpr int V1 = !F64 ? k2_vec32(VAR, true) : (MODE == kF64 ? k2_vec64(VAR, true) : VEC);
   constexpr int V0 = !F64 ? k2_vec32(VAR, false) : (MODE == kF64 ? k2_vec64(VAR, false) : VEC);
-  if constexpr (MLX_TUNE_K2_LDSACC && VAR != kVarSteric && (MODE == kF64 || MODE == kF32Faithful)) {
-    // the experiment: eta-only held-field passes, exact arithmetic, no dry skipping, z-profile
-    // pressure: 32 steps of one column (float64) / two columns (float32) per thread, sums in LDS
-    if (a.drho == nullptr && !skip && !fma && !a.p3d) {
-      k2_launch<TIn, F64 ? 1 : 2, F64 ? 32 : 16, VAR, MODE, false, false, false, false, true>(a);
-      return;
-    }
-  }
   // (one shape serves both where the two agree -- the float64 held-field passes: it then keeps its
   //  float32-egress twin)
   constexpr bool SAME = V0 == V1 && k2_nti(F64, VAR, true) == k2_nti(F64, VAR, false);
-  if (a.drho != nullptr) k2_flags<TIn, V1, k2_nti(F64, VAR, true), VAR, MODE, false>(a, skip, fma);
-  else k2_flags<TIn, V0, k2_nti(F64, VAR, false), VAR, MODE, false, SAME ? kDrBoth : kDrF64>(a, skip, fma);
+  if (a.drho != nullptr)
+    return k2_flags<TIn, V1, k2_nti(F64, VAR, true), VAR, MODE, false>(a, skip, fma);
+  return k2_flags<TIn, V0, k2_nti(F64, VAR, false), VAR, MODE, false, SAME ? kDrBoth : kDrF64>(a, skip, fma);
 }
 
 // Time steps per thread of the all-variants kernel (kNTI64All / kNTI32All below) -- except with
@@ -1635,21 +1617,22 @@ constexpr int k2_nti_all_f32out(int mode, int nti) {
 // VEC3/NTI3: columns and time steps per thread of the all-variants kernel (three sets of column
 // sums in registers)
 template <typename TIn, int VEC, int NTI1, int VEC3, int NTI3, int MODE, bool GEN>
-void k2_var(const K2Args& a, int var, bool skip, bool fma) {
+int k2_var(const K2Args& a, int var, bool skip, bool fma) {
   if (var == kVarAll) {
     constexpr int NTI3F = GEN ? NTI3 : k2_nti_all_f32out(MODE, NTI3);  // (its own time block: there)
     if constexpr (NTI3F != NTI3) {
-      if (a.drho32 && a.drho != nullptr) k2_flags<TIn, VEC3, NTI3F, kVarAll, MODE, GEN, kDrF32>(a, skip, fma);
-      else k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN, kDrF64>(a, skip, fma);
+      if (a.drho32 && a.drho != nullptr)
+        return k2_flags<TIn, VEC3, NTI3F, kVarAll, MODE, GEN, kDrF32>(a, skip, fma);
+      return k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN, kDrF64>(a, skip, fma);
     } else {
-      k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN>(a, skip, fma);
+      return k2_flags<TIn, VEC3, NTI3, kVarAll, MODE, GEN>(a, skip, fma);
     }
   } else if constexpr (GEN) {  // held fields reach the generic twin as stride-0 streams
-    k2_flags<TIn, VEC, NTI1, kVarSteric, MODE, GEN>(a, skip, fma);
+    return k2_flags<TIn, VEC, NTI1, kVarSteric, MODE, GEN>(a, skip, fma);
   } else {
-    if (var == kVarSteric) k2_single<TIn, VEC, kVarSteric, MODE>(a, skip, fma);
-    else if (var == kVarHalo) k2_single<TIn, VEC, kVarHalo, MODE>(a, skip, fma);
-    else k2_single<TIn, VEC, kVarThermo, MODE>(a, skip, fma);
+    if (var == kVarSteric) return k2_single<TIn, VEC, kVarSteric, MODE>(a, skip, fma);
+    if (var == kVarHalo) return k2_single<TIn, VEC, kVarHalo, MODE>(a, skip, fma);
+    return k2_single<TIn, VEC, kVarThermo, MODE>(a, skip, fma);
   }
 }
 
@@ -1657,6 +1640,23 @@ void k2_var(const K2Args& a, int var, bool skip, bool fma) {
 // come as float2 = 8-byte loads; four columns' worth of held parts and three sets of column sums
 // would not fit 256 VGPRs)
 constexpr int kNTI64All = 8, kNTI32All = 8, kNTIGenAll = 4, kVec32All = 2;
+
+// (float32 theta/S evaluated in float64 -- MLX_DTYPE_F32_UPCAST, or MLX_FLAG_FMA on float32 input
+//  -- were tried in the float64 kernel's shape, 2 columns x 16 steps with float2 loads, because
+//  four columns of float64 polynomial need 254 VGPRs: 64.6 ms instead of 43 for the upcast pass
+//  at the roofline grid, no change for the fused one -- 8-byte loads stream worse than they save.
+//  Neither is a default path.)
+int k2_dispatch(const K2Args& a, int dtype, bool fast, int var, bool skip, bool fma) {
+  return with_dtype(dtype, [&](auto tin, auto mode) {
+    using TIn = decltype(tin);
+    constexpr int MODE = decltype(mode)::value;
+    constexpr bool F64 = sizeof(TIn) == 8;  // the float64 kernel SHAPE
+    if (fast)
+      return k2_var<TIn, F64 ? kVec64 : kVec32, 0, F64 ? kVec64 : kVec32All,
+                    F64 ? kNTI64All : kNTI32All, MODE, false>(a, var, skip, fma);
+    return k2_var<TIn, 1, kNTIGen, 1, kNTIGenAll, MODE, true>(a, var, skip, fma);
+  });
+}
 
 // shared body of mlx_steric_local (var 0/1/2 from the strides) and mlx_steric_local_decomp (var 3)
 int steric_local_impl(const void* T, const void* S, const void* T0, const void* S0, int var,
@@ -1692,7 +1692,6 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
     if (eta_vstride < nt * plane || (delta_rho_out && drho_vstride < n4))
       return fail(MLX_E_SHAPE, "variant strides must be >= the size of one variant's field");
   }
-  const bool f64 = (dtype == MLX_DTYPE_F64) || mixed_dtype(dtype);  // the float64 kernel SHAPE
   // both strides must be whole packs too in the all-variants kernel (three fields, one base)
   bool fast = fast_layout(dtype, p_mode, eos, plane, sT, sS,
                           {T, S, T0, S0, rho0m, vol0_surface, eta_out, dz, dz ? nullptr : deptho,
@@ -1704,48 +1703,7 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
     if (eta_vstride % vec || drho_vstride % vec) fast = false;
   }
   if (var != kVarAll) var = (sT == 0) ? kVarHalo : ((sS == 0) ? kVarThermo : kVarSteric);
-  // (float32 theta/S evaluated in float64 -- MLX_DTYPE_F32_UPCAST, or MLX_FLAG_FMA on float32 input
-  //  -- were tried in the float64 kernel's shape, 2 columns x 16 steps with float2 loads, because
-  //  four columns of float64 polynomial need 254 VGPRs: 64.6 ms instead of 43 for the upcast pass
-  //  at the roofline grid, no change for the fused one -- 8-byte loads stream worse than they save.
-  //  Neither is a default path.)
-  const bool f32_fields = dtype == MLX_DTYPE_F32 || dtype == MLX_DTYPE_F32_UPCAST;
-  int v = !fast ? 1
-                : (var == kVarAll && !f64) ? kVec32All
-                : f32_fields ? k2_vec32(var, delta_rho_out != nullptr)
-                : (dtype == MLX_DTYPE_F64 && var != kVarAll) ? k2_vec64(var, delta_rho_out != nullptr)
-                             : vec_of(dtype);
-  int nti = (var == kVarAll) ? (fast ? (f64 ? kNTI64All : kNTI32All) : kNTIGenAll)
-                             : (fast ? k2_nti(f64, var, delta_rho_out != nullptr) : kNTIGen);
-  if (var == kVarAll && fast && drho32)  // (the float32-egress shape of the float64 polynomial)
-    nti = k2_nti_all_f32out(dtype == MLX_DTYPE_F64          ? kF64
-                            : dtype == MLX_DTYPE_F32_UPCAST ? kF32Upcast
-                            : dtype == MLX_DTYPE_F32        ? kF32Faithful
-                            : dtype == MLX_DTYPE_T32_S64    ? kMixT32
-                                                            : kMixS32,
-                            nti);
-  if (MLX_TUNE_K2_LDSACC && fast && (var == kVarHalo || var == kVarThermo) && !delta_rho_out &&
-      !skip && !fma && p_mode != MLX_P_FULL3D &&
-      (dtype == MLX_DTYPE_F64 || dtype == MLX_DTYPE_F32)) {  // (the experiment's shape: k2_single)
-    v = (dtype == MLX_DTYPE_F64) ? 1 : 2;
-    nti = (dtype == MLX_DTYPE_F64) ? 32 : 16;
-  }
-  if (ceil_div(nt, nti) > 65535) return fail(MLX_E_SHAPE, "nt too large for one call: chunk it");
-  const int64_t gx = ceil_div(plane, (int64_t)kBlock * v);
-  if (gx > 2147483647LL) return fail(MLX_E_SHAPE, "plane too large");
   K2Args a;
-  a.grid = dim3((unsigned)gx, (unsigned)ceil_div(nt, nti));
-  a.ntb_major = 0;
-  {  // time blocks of a tile side by side on one XCD (see the kernel) when there is more than one
-    const int64_t ntb = ceil_div(nt, nti);
-    const int64_t blocks = ceil_div(gx, 8) * 8 * ntb;
-    // (a HIP grid holds fewer than 2^32 THREADS: beyond 2^24 - 1 blocks of kBlock the 1-D form
-    //  would not launch where the (tiles, time blocks) grid does -- ADVICE r5)
-    if (MLX_TUNE_K2_TBMAJOR && ntb > 1 && blocks <= kK2MaxBlocks1D) {
-      a.grid = dim3((unsigned)blocks);
-      a.ntb_major = (int)ntb;
-    }
-  }
   a.st = (hipStream_t)stream;
   a.T = T; a.S = S; a.T0 = T0 ? T0 : T; a.S0 = S0 ? S0 : S;
   a.rho0m = rho0m; a.surf = vol0_surface; a.dz = dz; a.z_i = z_i;
@@ -1754,25 +1712,7 @@ int steric_local_impl(const void* T, const void* S, const void* T0, const void* 
   a.drho = delta_rho_out; a.eta = eta_out; a.drho_vstride = drho_vstride; a.eta_vstride = eta_vstride;
   a.drho32 = drho32;
   a.p3d = fast && p_mode == MLX_P_FULL3D;
-  if (fast) {
-    if (dtype == MLX_DTYPE_T32_S64)
-      k2_var<double, kVec64, 0, kVec64, kNTI64All, kMixT32, false>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T64_S32)
-      k2_var<double, kVec64, 0, kVec64, kNTI64All, kMixS32, false>(a, var, skip, fma);
-    else if (f64) k2_var<double, kVec64, 0, kVec64, kNTI64All, kF64, false>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_F32)
-      k2_var<float, kVec32, 0, kVec32All, kNTI32All, kF32Faithful, false>(a, var, skip, fma);
-    else k2_var<float, kVec32, 0, kVec32All, kNTI32All, kF32Upcast, false>(a, var, skip, fma);
-  } else {
-    if (dtype == MLX_DTYPE_F64) k2_var<double, 1, kNTIGen, 1, kNTIGenAll, kF64, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_F32)
-      k2_var<float, 1, kNTIGen, 1, kNTIGenAll, kF32Faithful, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T32_S64)
-      k2_var<double, 1, kNTIGen, 1, kNTIGenAll, kMixT32, true>(a, var, skip, fma);
-    else if (dtype == MLX_DTYPE_T64_S32)
-      k2_var<double, 1, kNTIGen, 1, kNTIGenAll, kMixS32, true>(a, var, skip, fma);
-    else k2_var<float, 1, kNTIGen, 1, kNTIGenAll, kF32Upcast, true>(a, var, skip, fma);
-  }
+  if (int rc = k2_dispatch(a, dtype, fast, var, skip, fma)) return rc;  // (a shape refusal)
   return hip_status(hipGetLastError(), "k_steric_local launch");
 }
 
@@ -1826,67 +1766,50 @@ static int eos_map_impl(const void* T, const void* S, int dtype, const double* p
   if (fma && func != MLX_FUNC_DENSITY)
     return fail(MLX_E_ENUM, "MLX_FLAG_FMA applies to the density only");
   hipStream_t st = (hipStream_t)stream;
-  const bool f64 = (dtype == MLX_DTYPE_F64);
-  const int vec = vec_of(dtype);
   const bool fast = fast_layout(dtype, p_mode, eos, plane, sT, sS, {T, S, out},
                                 func == MLX_FUNC_DENSITY ? p : nullptr) &&
-                    (f64 || func == MLX_FUNC_DENSITY) && func != MLX_FUNC_IBH;
+                    (dtype == MLX_DTYPE_F64 || func == MLX_FUNC_DENSITY) && func != MLX_FUNC_IBH;
   const bool p3d = fast && p_mode == MLX_P_FULL3D;
   const double* pp = p ? p : out;  // never dereferenced for the linear EOS
   for (int64_t tb = 0; tb < nt; tb += 32768) {
     const int64_t ntc = (nt - tb < 32768) ? (nt - tb) : 32768;
-    if (fast) {
-      constexpr int U = 2;
-      dim3 grid((unsigned)ceil_div(plane, (int64_t)kBlock * vec * U), (unsigned)nz, (unsigned)ntc);
-#define MLX_LAUNCH_K0P(TIN, VEC, MODE, FUNC, FMA, P3D)                                           \
-  hipLaunchKernelGGL((k_eos_map<TIN, VEC, U, MODE, FUNC, false, FMA, P3D>), grid, dim3(kBlock), \
-                     0, st, (const TIN*)T, (const TIN*)S, pp, p_mode, eos, func, nz, plane, sT,  \
-                     sS, tb, aux, out)
-// (the density map takes a (z,y,x) pressure field on the fast path too: P3D)
-#define MLX_LAUNCH_K0(TIN, VEC, MODE, FUNC, FMA)                                                 \
-  do {                                                                                           \
-    if constexpr (FUNC == kDensity) {                                                            \
-      if (p3d) { MLX_LAUNCH_K0P(TIN, VEC, MODE, FUNC, FMA, true); break; }                       \
-    }                                                                                            \
-    MLX_LAUNCH_K0P(TIN, VEC, MODE, FUNC, FMA, false);                                            \
-  } while (0)
-      if (f64) {
-        switch (func) {
-          case MLX_FUNC_DENSITY:
-            if (fma) MLX_LAUNCH_K0(double, 2, kF64, kDensity, true);
-            else MLX_LAUNCH_K0(double, 2, kF64, kDensity, false);
-            break;
-          case MLX_FUNC_DRHO_DTEMP: MLX_LAUNCH_K0(double, 2, kF64, kDrhoDtemp, false); break;
-          case MLX_FUNC_DRHO_DSAL: MLX_LAUNCH_K0(double, 2, kF64, kDrhoDsal, false); break;
-          case MLX_FUNC_ALPHA: MLX_LAUNCH_K0(double, 2, kF64, kAlpha, false); break;
-          default: MLX_LAUNCH_K0(double, 2, kF64, kBeta, false); break;
+    with_dtype(dtype, [&](auto tin, auto mode) {
+      using TIn = decltype(tin);
+      constexpr int MODE = decltype(mode)::value;
+      // (theta / S of different dtypes were refused above: the maps have no such kernels)
+      if constexpr (!IsMixed<MODE>::value) {
+        constexpr int VEC = 16 / sizeof(TIn), UF = 2, UG = 4;  // packs (fast) / cells (generic) per thread
+        auto launch = [&](auto kernel, int cells) {
+          dim3 grid((unsigned)ceil_div(plane, (int64_t)kBlock * cells), (unsigned)nz, (unsigned)ntc);
+          hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, (const TIn*)T, (const TIn*)S, pp,
+                             p_mode, eos, func, nz, plane, sT, sS, tb, aux, out);
+        };
+        // the fast kernels take the function at compile time; the density map takes a (z,y,x)
+        // pressure field on the fast path too (P3D)
+        auto fast_map = [&](auto fn, auto fm) {
+          constexpr int FUNC = decltype(fn)::value;
+          constexpr bool FMA = decltype(fm)::value;
+          if constexpr (FUNC == kDensity) {
+            if (p3d) return launch(k_eos_map<TIn, VEC, UF, MODE, FUNC, false, FMA, true>, VEC * UF);
+          }
+          launch(k_eos_map<TIn, VEC, UF, MODE, FUNC, false, FMA, false>, VEC * UF);
+        };
+        if (!fast) {
+          if (fma) launch(k_eos_map<TIn, 1, UG, MODE, 0, true, true>, UG);
+          else launch(k_eos_map<TIn, 1, UG, MODE, 0, true, false>, UG);
+        } else if (func == MLX_FUNC_DENSITY) {
+          if (fma) fast_map(Int<kDensity>{}, std::true_type{});
+          else fast_map(Int<kDensity>{}, std::false_type{});
+        } else if constexpr (sizeof(TIn) == 8) {  // (float32 fields: the density is the only fast map)
+          switch (func) {
+            case MLX_FUNC_DRHO_DTEMP: fast_map(Int<kDrhoDtemp>{}, std::false_type{}); break;
+            case MLX_FUNC_DRHO_DSAL: fast_map(Int<kDrhoDsal>{}, std::false_type{}); break;
+            case MLX_FUNC_ALPHA: fast_map(Int<kAlpha>{}, std::false_type{}); break;
+            default: fast_map(Int<kBeta>{}, std::false_type{}); break;
+          }
         }
-      } else if (fma) {
-        if (dtype == MLX_DTYPE_F32) MLX_LAUNCH_K0(float, 4, kF32Faithful, kDensity, true);
-        else MLX_LAUNCH_K0(float, 4, kF32Upcast, kDensity, true);
-      } else if (dtype == MLX_DTYPE_F32) {
-        MLX_LAUNCH_K0(float, 4, kF32Faithful, kDensity, false);
-      } else {
-        MLX_LAUNCH_K0(float, 4, kF32Upcast, kDensity, false);
       }
-#undef MLX_LAUNCH_K0
-#undef MLX_LAUNCH_K0P
-    } else {
-      constexpr int U = 4;
-      dim3 grid((unsigned)ceil_div(plane, (int64_t)kBlock * U), (unsigned)nz, (unsigned)ntc);
-#define MLX_LAUNCH_K0G(TIN, MODE, FMA)                                                           \
-  hipLaunchKernelGGL((k_eos_map<TIN, 1, U, MODE, 0, true, FMA>), grid, dim3(kBlock), 0, st,      \
-                     (const TIN*)T, (const TIN*)S, pp, p_mode, eos, func, nz, plane, sT, sS, tb, \
-                     aux, out)
-      if (fma) {
-        if (f64) MLX_LAUNCH_K0G(double, kF64, true);
-        else if (dtype == MLX_DTYPE_F32) MLX_LAUNCH_K0G(float, kF32Faithful, true);
-        else MLX_LAUNCH_K0G(float, kF32Upcast, true);
-      } else if (f64) MLX_LAUNCH_K0G(double, kF64, false);
-      else if (dtype == MLX_DTYPE_F32) MLX_LAUNCH_K0G(float, kF32Faithful, false);
-      else MLX_LAUNCH_K0G(float, kF32Upcast, false);
-#undef MLX_LAUNCH_K0G
-    }
+    });
   }
   return hip_status(hipGetLastError(), "mlx_eos_map launch");
 }

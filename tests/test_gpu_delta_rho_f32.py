@@ -28,7 +28,9 @@ pytestmark = pytest.mark.gpu
 SWITCH = "MOMLEVEL_AMD_DELTA_RHO_DTYPE"
 FUNCS = {"steric": steric, "thermosteric": thermosteric, "halosteric": halosteric}
 VARIANTS = ("steric", "thermosteric", "halosteric")
-SHAPES = [(6, 9, 14, 20), (3, 5, 7, 9), (5, 4, 7, 9), (17, 4, 6, 16)]
+# (17, 2, 2, 2052): the float32-egress shapes (16 steps, or 6 in the all-in-one pass, by 2 columns
+# per thread) on 9 column blocks and 2 or 3 time blocks, both ragged; the other planes fit one block
+SHAPES = [(6, 9, 14, 20), (3, 5, 7, 9), (5, 4, 7, 9), (17, 4, 6, 16), (17, 2, 2, 2052)]
 # (thetao dtype, so dtype, MOMLEVEL_AMD_F32_MODE)
 KINDS = {
     "f64": (np.float64, np.float64, None),

@@ -354,8 +354,11 @@ T32_S64, T64_S32 = (np.float32, np.float64), (np.float64, np.float32)  # fields 
 # Planes past one block of cells (K1 covers 2048 cells a block, 1024 on the scalar twin; K2
 # 256 x 2 or 256 x 4 columns): 2 x 2052 = 4104 cells, rows 16-byte aligned at either dtype -- two K1
 # blocks and 8 cells, 5 to 9 K2 blocks, the last ragged; 3 x 1367 = 4101 cells, odd: the scalar twins
-# over four blocks and 5 cells.  Both have land cells in the ragged tail.
-SEAM_SHAPES = [(9, 3, 2, 2052), (9, 3, 3, 1367)]
+# over four blocks and 5 cells.  Both have land cells in the ragged tail.  nt = 17 on the 4104-cell
+# plane: every fast K2 shape (6, 8, 12 or 16 steps per thread) then has 5 or 9 column blocks -- no
+# multiple of 8, the last ragged -- AND two or more time blocks, the last ragged: the 1-D
+# time-block-major grid with both seams at once.
+SEAM_SHAPES = [(9, 3, 2, 2052), (9, 3, 3, 1367), (17, 2, 2, 2052)]
 
 
 @pytest.mark.parametrize("skip_dry", [False, True])
