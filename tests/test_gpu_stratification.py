@@ -111,13 +111,14 @@ LEVELS = {
 @pytest.mark.parametrize("levels", sorted(LEVELS))
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("shape", [(3, 7, 6, 10), (2, 3, 5, 7), (9, 4, 8), (1, 12, 3, 64),
-                                   (2, 5, 1, 513)])
+                                   (2, 5, 1, 513), (2, 5, 2, 513)])
 def test_n2_bit_identical_to_numpy(shape, dtype, levels):
     """Every value of N^2 is numpy's: uneven and even level spacing (numpy.gradient's two
     branches), float64 and float32 fields (a float32 field's derivative is float32, alpha and beta
     float64), land / sub-bottom NaN, odd planes (the one-cell-per-thread kernel; 513 cells: over
-    three blocks, the last of one cell) and 16-byte ones, 3-D and 4-D layouts; the adjustment and
-    the wave speed on top."""
+    three blocks, the last of one cell) and 16-byte ones (2 x 513 = 1026 cells: the two-cell twin
+    over three blocks, the last of one thread), 3-D and 4-D layouts; the adjustment and the wave
+    speed on top."""
     nz = shape[-3]
     z = LEVELS[levels](nz)
     T, S = _fields(shape, dtype, seed=sum(shape) + nz)
@@ -147,14 +148,26 @@ def test_adjustment_and_wave_speed_on_an_odd_plane_of_three_blocks():
     one-cell-per-thread twin of the adjustment over three blocks, the surface as ``n2[0]``.  The
     field is drawn, not computed: a third of its values non-positive, land columns, sub-bottom NaN,
     a NaN surface above valid levels."""
-    shape = (5, 1, 513)
+    _adjustment_and_wave_speed((5, 1, 513))
+
+
+def test_adjustment_and_wave_speed_on_an_even_plane_of_three_blocks():
+    """the same assertions on 2 x 513 = 1026 cells, even and 16-byte aligned: the two-cell twin
+    over three blocks, the last of one thread -- whose pack, cells 1024 and 1025, holds the special
+    cases"""
+    _adjustment_and_wave_speed((5, 2, 513))
+
+
+def _adjustment_and_wave_speed(shape):
+    nz, plane = shape[0], shape[1] * shape[2]
     r = np.random.default_rng(513)
-    n2 = r.normal(1.0e-5, 2.0e-5, shape)
-    n2[:, :, r.random(513) < 0.2] = np.nan
-    n2[3:, :, r.random(513) < 0.3] = np.nan
-    n2[0, :, r.random(513) < 0.1] = np.nan
-    n2[:, :, 511], n2[0, :, 512], n2[2, :, 512] = np.nan, -1.0e-6, np.nan  # the last cells
-    assert (n2 <= 0.0).any() and np.isnan(n2[:, 0, 511]).all() and not np.isnan(n2[:, 0, 512]).all()
+    n2 = r.normal(1.0e-5, 2.0e-5, shape).reshape(nz, plane)
+    n2[:, r.random(plane) < 0.2] = np.nan
+    n2[3:, r.random(plane) < 0.3] = np.nan
+    n2[0, r.random(plane) < 0.1] = np.nan
+    n2[:, plane - 2], n2[0, plane - 1], n2[2, plane - 1] = np.nan, -1.0e-6, np.nan  # the last cells
+    assert (n2 <= 0.0).any() and np.isnan(n2[:, plane - 2]).all() and not np.isnan(n2[:, plane - 1]).all()
+    n2 = n2.reshape(shape)
     dz = np.abs(r.normal(10.0, 3.0, shape))
     dz[np.isnan(n2)] = np.nan
     dims = ("z_l", "yh", "xh")
