@@ -340,7 +340,7 @@ def _stratification(func, thetao, so, pres, eos, zcoord, gravity=-9.8):
     p = None if eos.lower() == "linear" else _strat_pressure(pres, thetao, zcoord, dev, f32)
     kw = dict(func=func, eos=eos.lower(), gravity=gravity)
     on_device = thetao.is_device or so.is_device
-    if not on_device and nt > 1 and nt * nz * plane > _HOST_PIPELINE_ELEMS:
+    if not on_device and hostio.wants_pipeline(nt, nt * nz * plane):
         out = _stratification_host_rows(thetao.data, so.data, p, z, nt, nz, plane, dev,
                                         lead=nt if zi == 1 else None, **kw)
         return DataArray(out.reshape(tuple(thetao.shape)), thetao.dims, dict(thetao.coords))
@@ -350,43 +350,9 @@ def _stratification(func, thetao, so, pres, eos, zcoord, gravity=-9.8):
     return DataArray(out if on_device else hostio.to_host(out), thetao.dims, dict(thetao.coords))
 
 
-# host fields above this size are evaluated in groups of rows (the dimensions before z: time
-# steps), the groups' uploads, kernels and result downloads overlapping -- as the pointwise EOS
-# functions do (eos/_dispatch.py) -- and the device never holds more than a few groups
-_HOST_PIPELINE_ELEMS = 1 << 26
-_HOST_GROUP_ELEMS = 1 << 25
-
-
-def _host_leading_groups(fields, nlead, rows, dev, kernel, out):
-    """``kernel`` on host fields, group of leading rows by group: the rows are independent, so
-    group k+1 uploads (hostio.Uploader) while group k's kernel runs and group k-1's result leaves
-    (hostio.Downloader), and the device never holds more than a few groups.  ``fields`` are sliced
-    along their own leading axis (length ``nlead``) as they are -- a lazy field (dask / netCDF4 /
-    h5py-like) is read group by group in the upload worker and never materialised whole;
-    ``kernel(tensors, i0, i1)`` returns the device result of rows [i0, i1), which lands in
-    ``out[i0:i1]``."""
-    bounds = [(i0, min(i0 + rows, nlead)) for i0 in range(0, nlead, rows)]
-    main = torch.cuda.current_stream(dev)
-    up = hostio.Uploader(dev)
-    try:
-        with hostio.Downloader(dev) as results:
-            nxt = up.submit([hostio.leading_slice(f, *bounds[0]) for f in fields])
-            for n, (i0, i1) in enumerate(bounds):
-                tensors, ready = nxt.result()  # (re-raises what the worker raised)
-                if n + 1 < len(bounds):
-                    j0, j1 = bounds[n + 1]
-                    nxt = up.submit([hostio.leading_slice(f, j0, j1) for f in fields])
-                main.wait_event(ready)
-                res = kernel(tensors, i0, i1)
-                results.submit([(out[i0:i1], res.reshape(out[i0:i1].shape))])
-    finally:
-        up.close()
-    return out
-
-
 def _stratification_host_rows(T, S, p, z, nt, nz, plane, dev, lead=None, **kw):
     """core.stratification on host fields seen as (nt, nz, plane), group of rows by group
-    (_host_leading_groups: rows are independent, the derivative runs along z).  ``lead``: the
+    (hostio.pipeline_rows: rows are independent, the derivative runs along z).  ``lead``: the
     fields are (lead, nz, ...) with ONE dimension before z (the usual (time, z, y, x)): they are
     then sliced along it as they are -- a lazy field is read group by group and never materialised
     whole.  (A pressure that varies from row to row -- ``p`` of shape (nt, nz, plane) -- IS
@@ -397,7 +363,6 @@ def _stratification_host_rows(T, S, p, z, nt, nz, plane, dev, lead=None, **kw):
     else:
         Tn = hostio.as_plain(T[...] if is_lazy(T) else T).reshape(nt, nz, plane)
         Sn = hostio.as_plain(S[...] if is_lazy(S) else S).reshape(nt, nz, plane)
-    rows = max(1, _HOST_GROUP_ELEMS // (nz * plane))
     p_rows = isinstance(p, torch.Tensor) and p.dim() == 3  # a pressure that varies from row to row
 
     def kernel(tensors, i0, i1):
@@ -405,8 +370,8 @@ def _stratification_host_rows(T, S, p, z, nt, nz, plane, dev, lead=None, **kw):
         return core.stratification(Td.reshape(i1 - i0, nz, plane), Sd.reshape(i1 - i0, nz, plane),
                                    p[i0:i1] if p_rows else p, z, **kw)
 
-    return _host_leading_groups([Tn, Sn], nt, rows, dev, kernel,
-                                np.empty((nt, nz, plane), dtype=np.float64))
+    return hostio.pipeline_rows(hostio.row_bounds(nt, nz * plane), dev, hostio.leading_slices([Tn, Sn]),
+                                kernel, np.empty((nt, nz, plane), dtype=np.float64))
 
 
 @accepts_xarray
@@ -525,7 +490,7 @@ def _coord_names(coord_dict):
     return {k: coord_dict[k] for k in _COORD_KEYS}
 
 
-def _float_name(da, what, allow_other=False):
+def float_name(da, what, allow_other=False):
     """"float32" / "float64"; float16, long double (check_field_dtype) and, unless
     ``allow_other``, everything that is not a float are refused"""
     name = check_field_dtype(da.dtype, what)
@@ -536,7 +501,7 @@ def _float_name(da, what, allow_other=False):
     return name
 
 
-def _trailing(da, ydim, xdim, what):
+def check_trailing(da, ydim, xdim, what):
     if len(da.dims) < 2 or tuple(da.dims[-2:]) != (ydim, xdim):
         raise ValueError(f"{what} has dims {da.dims}: its last two must be ({ydim!r}, {xdim!r}), "
                          "in that order")
@@ -567,7 +532,7 @@ def _records(x, dev, dtype, nrec, tail):
 def _stencil(fields, lead_shape, out_tail, out_np_dtype, dev, on_device, kernel):
     """``kernel(tensors)`` on the (nrec, y, x) views of ``fields`` (labelled arrays that share
     ``lead_shape``), whole or -- large host / lazy fields with more than one leading row -- in
-    groups of whole leading rows (_host_leading_groups).  Returns the raw result at
+    groups of whole leading rows (hostio.pipeline_rows).  Returns the raw result at
     lead_shape + out_tail: host in, host out."""
     shape = tuple(lead_shape) + tuple(out_tail)
     nrec = int(np.prod(lead_shape, dtype=np.int64))
@@ -576,16 +541,16 @@ def _stencil(fields, lead_shape, out_tail, out_np_dtype, dev, on_device, kernel)
     def views(tensors, n):
         return [t.reshape((n,) + tuple(f.shape[-2:])) for t, f in zip(tensors, fields)]
 
-    if (not on_device and len(lead_shape) >= 1 and lead_shape[0] > 1
-            and int(np.prod(shape, dtype=np.int64)) > _HOST_PIPELINE_ELEMS):
+    if (not on_device and len(lead_shape) >= 1
+            and hostio.wants_pipeline(lead_shape[0], int(np.prod(shape, dtype=np.int64)))):
         inner = int(np.prod(lead_shape[1:], dtype=np.int64))
-        rows = max(1, _HOST_GROUP_ELEMS // max(1, int(np.prod(shape[1:], dtype=np.int64))))
+        bounds = hostio.row_bounds(lead_shape[0], int(np.prod(shape[1:], dtype=np.int64)))
         sources = [f.data if f.is_lazy else f.values for f in fields]
-        out = np.empty(shape, dtype=out_np_dtype)
-        return _host_leading_groups(
-            sources, lead_shape[0], rows, dev,
+        return hostio.pipeline_rows(
+            bounds, dev, hostio.leading_slices(sources),
             lambda tensors, i0, i1: kernel(views([t.to(d) for t, d in zip(tensors, tdt)],
-                                                 (i1 - i0) * inner)), out)
+                                                 (i1 - i0) * inner)),
+            np.empty(shape, dtype=out_np_dtype))
     tensors = [_records(_raw(f), dev, d, nrec, f.shape[-2:]) for f, d in zip(fields, tdt)]
     res = kernel(tensors).reshape(shape)
     return res if on_device else hostio.to_host(res)
@@ -624,8 +589,8 @@ def calc_rel_vort(dset, varname_map=None, coord_dict=None, symmetric=False):
     names = _coord_names(coord_dict)
     u, v, dx, dy, area = (dset[varname_map[k]] for k in ("u", "v", "dx", "dy", "area"))
     yc, xc, yq, xq = names["ycenter"], names["xcenter"], names["ycorner"], names["xcorner"]
-    _trailing(u, yc, xq, varname_map["u"])
-    _trailing(v, yq, xc, varname_map["v"])
+    check_trailing(u, yc, xq, varname_map["u"])
+    check_trailing(v, yq, xc, varname_map["v"])
     for m, dims, what in ((dx, (yc, xq), varname_map["dx"]), (dy, (yq, xc), varname_map["dy"]),
                           (area, (yq, xq), varname_map["area"])):
         if tuple(m.dims) != dims:
@@ -639,11 +604,11 @@ def calc_rel_vort(dset, varname_map=None, coord_dict=None, symmetric=False):
             if sizes.setdefault(d, n) != n:
                 raise ValueError(f"{d!r} has {n} points in one field and {sizes[d]} in another")
     ny, nx = _corner_extents(sizes, names, symmetric, "calc_rel_vort")
-    fdt = _float_name(u, "velocity fields")
-    if _float_name(v, "velocity fields") != fdt:
+    fdt = float_name(u, "velocity fields")
+    if float_name(v, "velocity fields") != fdt:
         raise TypeError(f"{varname_map['u']} is {u.dtype} and {varname_map['v']} is {v.dtype}: "
                         "convert one of them")
-    mdts = {_float_name(m, "grid metrics") for m in (dx, dy, area)}
+    mdts = {float_name(m, "grid metrics") for m in (dx, dy, area)}
     if len(mdts) != 1:
         raise TypeError(f"{varname_map['dx']}, {varname_map['dy']} and {varname_map['area']} must "
                         f"share one dtype, not {sorted(mdts)}")
@@ -678,8 +643,8 @@ def calc_pv(zeta, coriolis, n2, gravity=9.8, coord_dict=None, symmetric=False, u
     yc, xc, yq, xq = names["ycenter"], names["xcenter"], names["ycorner"], names["xcorner"]
     interp = bool(interp_n2)
     if interp:
-        _trailing(zeta, yq, xq, "zeta")
-        _trailing(n2, yc, xc, "n2")
+        check_trailing(zeta, yq, xq, "zeta")
+        check_trailing(n2, yc, xc, "n2")
         if tuple(coriolis.dims) != (yq, xq):
             raise ValueError(f"coriolis has dims {coriolis.dims}: expected {(yq, xq)}")
     else:
@@ -700,8 +665,8 @@ def calc_pv(zeta, coriolis, n2, gravity=9.8, coord_dict=None, symmetric=False, u
         _corner_extents(sizes, names, symmetric, "calc_pv")
     elif tuple(n2.shape[-2:]) != (ny, nx):
         raise ValueError(f"n2 {tuple(n2.shape)} and zeta {tuple(zeta.shape)} differ in shape")
-    zdt, ndt = _float_name(zeta, "zeta"), _float_name(n2, "n2")
-    cdt = _float_name(coriolis, "coriolis", allow_other=True)
+    zdt, ndt = float_name(zeta, "zeta"), float_name(n2, "n2")
+    cdt = float_name(coriolis, "coriolis", allow_other=True)
     dev = engine.device_of(zeta.data, n2.data, coriolis.data)
     on_device = zeta.is_device or n2.is_device
     fd = engine.to_device(_raw(coriolis), dev,
@@ -744,8 +709,8 @@ def calc_rossby_rd(wave_speed, coriolis):
     outer = int(np.prod(shape[:start], dtype=np.int64))
     plane = int(np.prod(shape[start:start + nd], dtype=np.int64))
     inner = int(np.prod(shape[start + nd:], dtype=np.int64))
-    wdt = _float_name(wave_speed, "wave_speed", allow_other=True)
-    cdt = _float_name(coriolis, "coriolis", allow_other=True)
+    wdt = float_name(wave_speed, "wave_speed", allow_other=True)
+    cdt = float_name(coriolis, "coriolis", allow_other=True)
     dev = engine.device_of(wave_speed.data, coriolis.data)
     c = engine.to_device(_raw(wave_speed), dev, torch.float32 if wdt == "float32" else torch.float64)
     f = engine.to_device(_raw(coriolis), dev, torch.float32 if cdt == "float32" else torch.float64)

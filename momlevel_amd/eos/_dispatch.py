@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import core, hostio
-from ..labeled import check_field_dtype
+from ..labeled import check_field_dtype, is_lazy
 
 
 def _as_tensor(x, device):
@@ -30,15 +30,8 @@ def _as_tensor(x, device):
     return hostio.to_device(a, device)  # through our own page-locked staging
 
 
-def _is_lazy(x):
-    """array-shaped, readable only by slicing (dask / netCDF4 / h5py-like): never np.asarray'ed
-    whole here -- the piecewise evaluation reads it piece by piece"""
-    return (not isinstance(x, (np.ndarray, np.generic, torch.Tensor, list, tuple, bool, int, float))
-            and all(hasattr(x, a) for a in ("shape", "dtype", "__getitem__")))
-
-
 def _shape(x):
-    return tuple(x.shape) if _is_lazy(x) else np.shape(x)
+    return tuple(x.shape) if is_lazy(x) else np.shape(x)
 
 
 def _is_weak(x):
@@ -59,7 +52,7 @@ def _kind(x):
         return None
     if _is_weak(x):
         return "weak"
-    dt = x.dtype if isinstance(x, torch.Tensor) or _is_lazy(x) else hostio.as_plain(x).dtype
+    dt = x.dtype if isinstance(x, torch.Tensor) or is_lazy(x) else hostio.as_plain(x).dtype
     name = check_field_dtype(dt, "operands")  # (byte order does not matter: ">f4" is float32)
     return "f32" if name == "float32" else "f64"
 
@@ -76,64 +69,36 @@ def _tuned_kernel_covers(kT, kS, kp, eos):
     return eos != "linear" and kT == "f32" and kS == "f32" and kp == "f64"
 
 
-# host arrays above this size are evaluated in pieces along their leading axis, the pieces'
-# uploads, kernels and result downloads overlapping (the link is full duplex)
-_HOST_PIPELINE_ELEMS = 1 << 26
-_HOST_CHUNK_ELEMS = 1 << 25  # 256 MiB of float64 per operand and piece
-
-
 def _host_pipeline(operands, kernel):
-    """Large host arrays: walk the leading axis of the broadcast shape in pieces.  Piece k+1 is
-    staged and uploaded by a worker thread (hostio.Uploader) while piece k's kernel runs and piece
-    k-1's result leaves on another (hostio.Downloader): both directions of the host link are busy
-    at once, and the device never holds more than a few pieces (the result is a host array
-    anyway).
+    """Large host arrays: walk the leading axis of the broadcast shape in pieces, the pieces'
+    uploads, kernels and result downloads overlapping (hostio.pipeline_rows).
 
     ``operands``: host arrays, lazy sources, python scalars or None (an operand that is absent);
     ``kernel(ops)``: the per-piece evaluation -- ``ops`` are the operands of one piece in the same
     order, the arrays among them as device tensors -- returning a device tensor of the piece's
     shape."""
-    arrs = [x if (_is_weak(x) or _is_lazy(x)) else np.asarray(x)
+    arrs = [x if (_is_weak(x) or is_lazy(x)) else np.asarray(x)
             for x in (0.0 if x is None else x for x in operands)]
     shape = np.broadcast_shapes(*(_shape(a) for a in arrs))
-    rows = max(1, _HOST_CHUNK_ELEMS // max(1, int(np.prod(shape[1:]))))
-    bounds = [(i0, min(i0 + rows, shape[0])) for i0 in range(0, shape[0], rows)]
-    device = torch.device("cuda", torch.cuda.current_device())
-    main = torch.cuda.current_stream(device)
+    travel = [k for k, x in enumerate(operands) if x is not None and not _is_weak(x)]
 
     def part(a, i0, i1):  # slice the leading axis unless the operand broadcasts along it
         if len(_shape(a)) == len(shape) and a.shape[0] == shape[0] and shape[0] > 1:
             return hostio.leading_slice(a, i0, i1)  # (a lazy operand is READ piece by piece, by the upload worker)
-        return hostio.as_plain(a[...]) if _is_lazy(a) else a
+        return hostio.as_plain(a[...]) if is_lazy(a) else a  # (re-sent whole with every piece)
 
-    def pieces(i0, i1):  # (operands of the piece, which of them travel)
-        ops = [None if x is None else part(a, i0, i1) for x, a in zip(operands, arrs)]
-        return ops, [k for k, x in enumerate(ops) if x is not None and not _is_weak(x)]
+    def piece(tensors, i0, i1):
+        ops = list(operands)
+        for k, t in zip(travel, tensors):
+            ops[k] = t
+        return kernel(ops)
 
-    out = None
-    up = hostio.Uploader(device)
-    try:
-        with hostio.Downloader(device) as results:
-            ops, travel = pieces(*bounds[0])
-            nxt = up.submit([ops[k] for k in travel])
-            for n, (i0, i1) in enumerate(bounds):
-                tensors, ready = nxt.result()  # (re-raises what the worker raised)
-                cur, cur_travel = ops, travel
-                if n + 1 < len(bounds):
-                    ops, travel = pieces(*bounds[n + 1])
-                    nxt = up.submit([ops[k] for k in travel])
-                main.wait_event(ready)
-                for k, t in zip(cur_travel, tensors):
-                    cur[k] = t
-                res = kernel(cur)  # device tensor
-                if out is None:
-                    # (a mapping of our own when large, pooled across calls: hostio.result_array)
-                    out = hostio.result_array(shape, np.float32 if res.dtype == torch.float32
-                                              else np.float64)
-                results.submit([(out[i0:i1], res.reshape(out[i0:i1].shape))])
-    finally:
-        up.close()
-    return out
+    # (the result: a mapping of our own when large, pooled across calls)
+    return hostio.pipeline_rows(
+        hostio.row_bounds(shape[0], int(np.prod(shape[1:]))),
+        torch.device("cuda", torch.cuda.current_device()),
+        lambda i0, i1: [part(arrs[k], i0, i1) for k in travel], piece,
+        lambda dt: hostio.result_array(shape, np.float32 if dt == torch.float32 else np.float64))
 
 
 def _evaluate_host_chunked(eos, func, T, S, p, gravity):
@@ -178,9 +143,9 @@ def evaluate(eos, func, T, S, p, gravity=None):
     T, S, p = (hostio.as_plain(x) if isinstance(x, np.ma.MaskedArray) else x for x in (T, S, p))
     if not any(isinstance(x, torch.Tensor) for x in (T, S, p)):
         shape = np.broadcast_shapes(*(_shape(x) for x in (T, S, p) if x is not None))
-        if len(shape) >= 1 and int(np.prod(shape)) > _HOST_PIPELINE_ELEMS and shape[0] > 1:
+        if len(shape) >= 1 and hostio.wants_pipeline(shape[0], int(np.prod(shape))):
             return _evaluate_host_chunked(eos, func, T, S, p, gravity)
-        T, S, p = (hostio.as_plain(x[...]) if _is_lazy(x) else x for x in (T, S, p))
+        T, S, p = (hostio.as_plain(x[...]) if is_lazy(x) else x for x in (T, S, p))
     on_device = any(isinstance(x, torch.Tensor) and x.is_cuda for x in (T, S, p))
     scalar_in = all(np.ndim(x) == 0 and not isinstance(x, torch.Tensor) for x in (T, S, p))
     device = next(

@@ -721,6 +721,58 @@ class Uploader:
         self._pool.shutdown(wait=True)
 
 
+# host arrays and lazy sources above PIPELINE_ELEMS elements are evaluated in groups of leading rows
+# of about PIECE_ELEMS elements (256 MiB of float64 per operand and group): pipeline_rows
+PIPELINE_ELEMS = 1 << 26
+PIECE_ELEMS = 1 << 25
+
+
+def wants_pipeline(nlead, elems):
+    """Whether a host computation of ``elems`` elements with ``nlead`` leading rows goes in groups"""
+    return nlead > 1 and elems > PIPELINE_ELEMS
+
+
+def row_bounds(nlead, elems_per_row):
+    """[(i0, i1)]: the ``nlead`` leading rows in groups of about PIECE_ELEMS elements, one row at least"""
+    rows = max(1, PIECE_ELEMS // max(1, elems_per_row))
+    return [(i0, min(i0 + rows, nlead)) for i0 in range(0, nlead, rows)]
+
+
+def leading_slices(fields):
+    """The ``stage`` of pipeline_rows for ``fields`` that are sliced along their own leading axis as
+    they are: a lazy field is read group by group in the upload worker, never materialised whole."""
+    return lambda i0, i1: [leading_slice(f, i0, i1) for f in fields]
+
+
+def pipeline_rows(bounds, device, stage, kernel, out):
+    """``kernel`` on host data, group of leading rows by group (``bounds``: row_bounds).  The rows
+    are independent, so group k+1 is staged and uploaded by a worker thread (Uploader) while group
+    k's kernel runs and group k-1's result leaves on another (Downloader): both directions of the
+    host link are busy at once and the device never holds more than a few groups.
+
+    ``stage(i0, i1)``: the host arrays / deferred slices (leading_slice) that travel for rows
+    [i0, i1); ``kernel(tensors, i0, i1)``: their device tensors, in order -> the device result of
+    those rows, which lands in ``out[i0:i1]``.  ``out``: the host array of the whole result, or a
+    function that allocates it from the first result's torch dtype.  Returns the array."""
+    main = torch.cuda.current_stream(device)
+    up = Uploader(device)
+    try:
+        with Downloader(device) as results:
+            nxt = up.submit(stage(*bounds[0]))
+            for n, (i0, i1) in enumerate(bounds):
+                tensors, ready = nxt.result()  # (re-raises what the worker raised)
+                if n + 1 < len(bounds):
+                    nxt = up.submit(stage(*bounds[n + 1]))
+                main.wait_event(ready)
+                res = kernel(tensors, i0, i1)
+                if callable(out):
+                    out = out(res.dtype)
+                results.submit([(out[i0:i1], res.reshape(out[i0:i1].shape))])
+    finally:
+        up.close()
+    return out
+
+
 def to_host(t):
     """Device tensor -> numpy array (through the staging ring when not small; synchronises)."""
     if not (isinstance(t, torch.Tensor) and t.is_cuda):

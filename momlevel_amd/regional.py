@@ -108,7 +108,7 @@ class _Maps:
         self.src = areacello
         self.dims = tuple(areacello.dims)
         self.shape = tuple(int(n) for n in areacello.shape)
-        name = derived._float_name(areacello, "areacello", allow_other=True)
+        name = derived.float_name(areacello, "areacello", allow_other=True)
         # (a device-resident map is small: downloaded for the check)
         area = np.ascontiguousarray(areacello.values,
                                     dtype=np.float32 if name == "float32" else np.float64)
@@ -188,7 +188,7 @@ def _records(da, maps, want_anomaly):
     """(mean, den, anomaly or None) of one DataArray as raw arrays -- (lead..., nslots) and the
     input's shape -- on the device for a device record, on the host otherwise."""
     ydim, xdim = maps.dims
-    derived._trailing(da, ydim, xdim, da.name or "the record")
+    derived.check_trailing(da, ydim, xdim, da.name or "the record")
     if tuple(int(n) for n in da.shape[-2:]) != maps.shape:
         raise ValueError(f"the record's plane {tuple(da.shape[-2:])} is not areacello's {maps.shape}")
     name = check_field_dtype(da.dtype, "records")
@@ -200,14 +200,16 @@ def _records(da, maps, want_anomaly):
     dev = engine.device_of(da.data, maps.src.data)
     on_device = da.is_device
 
-    if (not on_device and len(lead) >= 1 and lead[0] > 1
-            and nrec * plane > derived._HOST_PIPELINE_ELEMS):
+    if not on_device and len(lead) >= 1 and hostio.wants_pipeline(lead[0], nrec * plane):
         # a large host / lazy record: groups of whole leading rows, uploads, kernels and downloads
         # overlapping; a lazy record is never materialised whole.  A record's means depend on that
         # record alone, so the grouping cannot show in the result.
         inner = nrec // lead[0]
-        rows = max(1, derived._HOST_GROUP_ELEMS // max(1, inner * plane))
         source = da.data if da.is_lazy else da.values
+
+        def groups(kernel, out):
+            return hostio.pipeline_rows(hostio.row_bounds(lead[0], inner * plane), dev,
+                                        hostio.leading_slices([source]), kernel, out)
 
         def stats(tensors, i0, i1):
             v = tensors[0].to(tdt).reshape((i1 - i0) * inner, plane)
@@ -223,8 +225,7 @@ def _records(da, maps, want_anomaly):
                 den_d[i0 * inner:i1 * inner] = d
                 return maps.anomaly(v, m, dev)
 
-            anom = derived._host_leading_groups([source], lead[0], rows, dev, kernel,
-                                                np.empty(lead + maps.shape, dtype=np.float64))
+            anom = groups(kernel, np.empty(lead + maps.shape, dtype=np.float64))
             mean, den = hostio.to_host(mean_d), hostio.to_host(den_d)
         else:
             def kernel(tensors, i0, i1):
@@ -232,8 +233,7 @@ def _records(da, maps, want_anomaly):
                 return torch.stack([m.reshape(i1 - i0, inner, ns), d.reshape(i1 - i0, inner, ns)],
                                    dim=1)
 
-            both = derived._host_leading_groups([source], lead[0], rows, dev, kernel,
-                                                np.empty((lead[0], 2, inner, ns), dtype=np.float64))
+            both = groups(kernel, np.empty((lead[0], 2, inner, ns), dtype=np.float64))
             mean, den, anom = both[:, 0], both[:, 1], None
         return mean.reshape(lead + (ns,)), den.reshape(lead + (ns,)), anom
 

@@ -18,6 +18,7 @@ import torch
 
 from .. import core, hostio
 from ..eos import _dispatch
+from ..labeled import is_lazy
 
 __all__ = ["spice"]
 
@@ -52,8 +53,8 @@ def spice(thetao, so):
     so = np.array([float(so)]) if isinstance(so, (float, int)) else so
     # a numpy masked array (a netCDF4 read) means NaN where it is masked
     thetao, so = (hostio.as_plain(x) if isinstance(x, np.ma.MaskedArray) else x for x in (thetao, so))
-    if not all(isinstance(x, torch.Tensor) or _dispatch._is_lazy(x) for x in (thetao, so)):
-        thetao, so = (x if isinstance(x, torch.Tensor) or _dispatch._is_lazy(x) else np.asarray(x)
+    if not all(isinstance(x, torch.Tensor) or is_lazy(x) for x in (thetao, so)):
+        thetao, so = (x if isinstance(x, torch.Tensor) or is_lazy(x) else np.asarray(x)
                       for x in (thetao, so))
     shape = _dispatch._shape(thetao)
     assert shape == _dispatch._shape(so), "thetao and so must have the same shape"
@@ -62,11 +63,11 @@ def spice(thetao, so):
 
     tensors = [x for x in (thetao, so) if isinstance(x, torch.Tensor)]
     if not tensors:
-        if len(shape) >= 1 and int(np.prod(shape)) > _dispatch._HOST_PIPELINE_ELEMS and shape[0] > 1:
+        if len(shape) >= 1 and hostio.wants_pipeline(shape[0], int(np.prod(shape))):
             device = torch.device("cuda", torch.cuda.current_device())
             return _dispatch._host_pipeline(
                 [thetao, so], lambda ops: _on_device(ops[0], ops[1], device))
-        thetao, so = (hostio.as_plain(x[...]) if _dispatch._is_lazy(x) else x for x in (thetao, so))
+        thetao, so = (hostio.as_plain(x[...]) if is_lazy(x) else x for x in (thetao, so))
     device = next((x.device for x in tensors if x.is_cuda),
                   torch.device("cuda", torch.cuda.current_device()))
     out = _on_device(thetao, so, device)

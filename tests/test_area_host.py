@@ -222,7 +222,7 @@ def test_grouping_above_the_cap():
 def on_numpy(monkeypatch):
     def records(da, maps, want_anomaly):
         ydim, xdim = maps.dims
-        regional.derived._trailing(da, ydim, xdim, da.name or "the record")
+        regional.derived.check_trailing(da, ydim, xdim, da.name or "the record")
         v, area = da.values, maps.area.reshape(maps.shape)
         if maps.ids is None:
             mean, den = an.area_mean(v, area)

@@ -260,8 +260,8 @@ def test_host_input_equals_device_input(monkeypatch):
         return real(self, arrays)
 
     monkeypatch.setattr(hostio.Uploader, "submit", counting)
-    monkeypatch.setattr(derived, "_HOST_PIPELINE_ELEMS", 100)
-    monkeypatch.setattr(derived, "_HOST_GROUP_ELEMS", 2 * nz * shape[0] * shape[1])  # two steps a group
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 100)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * nz * shape[0] * shape[1])  # two steps a group
     for src in (host, DataArray(CountingLazy(v), dims)):
         pieces.clear()
         m, d = regional.area_mean(src, a, regions=label, return_area=True)

@@ -59,15 +59,15 @@ def test_calc_rho_on_a_lazy_field(monkeypatch):
     -- piece by piece along its leading axis when it is large (eos/_dispatch.py), whole when small
     or when it has to be transposed first"""
     from lazy_array import CountingLazy
-    from momlevel_amd.eos import _dispatch
+    from momlevel_amd import hostio
 
     ref = o.calc_rho(dset1.thetao.values, dset1.so.values, dset1.z_l.values * 1.0e4)
     lazy = CountingLazy(dset1.thetao.values)
     rho = derived.calc_rho(DataArray(lazy, dset1.thetao.dims, dict(dset1.thetao.coords)), dset1.so,
                            dset1.z_l * 1.0e4)
     assert_bit_equal(rho.values, ref)
-    monkeypatch.setattr(_dispatch, "_HOST_PIPELINE_ELEMS", 100)
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 2 * 125)  # two time steps a piece
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 100)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 125)  # two time steps a piece
     lazy = CountingLazy(dset1.thetao.values)
     rho = derived.calc_rho(DataArray(lazy, dset1.thetao.dims, dict(dset1.thetao.coords)), dset1.so,
                            dset1.z_l * 1.0e4)
@@ -87,7 +87,8 @@ def test_calc_rho_on_masked_arrays(monkeypatch):
     a lazy field (small: read whole; large: piece by piece in the upload worker), as a field that
     must be transposed, and handed straight to the numpy-level EOS function."""
     from lazy_array import MaskedLazy, as_masked
-    from momlevel_amd.eos import _dispatch, wright
+    from momlevel_amd import hostio
+    from momlevel_amd.eos import wright
 
     T = dset1.thetao.values.copy()
     S = dset1.so.values.copy()
@@ -108,8 +109,8 @@ def test_calc_rho_on_masked_arrays(monkeypatch):
     assert_bit_equal(got, ref)
     f32 = wright.density(as_masked(T.astype(np.float32)), as_masked(S.astype(np.float32)), p[:, None, None])
     assert_bit_equal(f32, o.calc_rho(T.astype(np.float32), S.astype(np.float32), p))
-    monkeypatch.setattr(_dispatch, "_HOST_PIPELINE_ELEMS", 100)
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 2 * 125)  # two time steps a piece
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 100)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 125)  # two time steps a piece
     lazy = MaskedLazy(T)
     rho = derived.calc_rho(DataArray(lazy, dims, coords), DataArray(as_masked(S), dims, coords), pres)
     assert_bit_equal(rho.values, ref)

@@ -225,7 +225,6 @@ def test_placement_shapes_and_dtypes():
 def test_the_host_pipeline_walks_pieces(monkeypatch):
     from lazy_array import CountingLazy, MaskedLazy
     from momlevel_amd import hostio
-    from momlevel_amd.eos import _dispatch
 
     rng = np.random.default_rng(11)
     shape = (6, 5, 9, 11)
@@ -245,8 +244,8 @@ def test_the_host_pipeline_walks_pieces(monkeypatch):
         return real(self, arrays)
 
     monkeypatch.setattr(hostio.Uploader, "submit", counting)
-    monkeypatch.setattr(_dispatch, "_HOST_PIPELINE_ELEMS", 1000)
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 2 * 5 * 9 * 11)  # two rows of the leading axis a piece
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 1000)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 5 * 9 * 11)  # two rows of the leading axis a piece
     got = spice(T, S)
     assert type(got) is np.ndarray and got.dtype == np.float64
     assert_bit_equal(got, whole)
@@ -304,11 +303,11 @@ def test_calc_spice_broadcasts_by_dimension_name():
 
 def test_calc_spice_on_lazy_fields(monkeypatch):
     from lazy_array import CountingLazy
-    from momlevel_amd.eos import _dispatch
+    from momlevel_amd import hostio
 
     ref = derived.calc_spice(dset1.thetao, dset1.so).values
-    monkeypatch.setattr(_dispatch, "_HOST_PIPELINE_ELEMS", 100)
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 2 * 125)  # two time steps a piece
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 100)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 125)  # two time steps a piece
     lazy = CountingLazy(dset1.thetao.values)
     pi = derived.calc_spice(DataArray(lazy, dset1.thetao.dims, dict(dset1.thetao.coords)), dset1.so)
     assert_bit_equal(pi.values, ref)

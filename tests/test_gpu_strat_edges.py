@@ -528,8 +528,8 @@ def test_host_pipeline_of_member_time_fields(monkeypatch):
     plane = cells[0] * cells[1]
     whole = run()
     assert (2, NZ, plane) not in used  # nothing went group by group
-    monkeypatch.setattr(derived, "_HOST_PIPELINE_ELEMS", 1000)
-    monkeypatch.setattr(derived, "_HOST_GROUP_ELEMS", 2 * NZ * plane)  # two rows a group
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 1000)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * NZ * plane)  # two rows a group
     used.clear()
     piped = run()
     assert used == [(2, NZ, plane)] * 9  # three calls, six rows each, in groups of two

@@ -213,8 +213,8 @@ def test_large_host_fields_are_pipelined(monkeypatch):
     size; a pressure that varies with time is sliced with its rows."""
     from momlevel_amd import hostio
 
-    monkeypatch.setattr(derived, "_HOST_PIPELINE_ELEMS", 1000)
-    monkeypatch.setattr(derived, "_HOST_GROUP_ELEMS", 2 * 6 * 40 * 50)  # two time steps a group
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 1000)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 6 * 40 * 50)  # two time steps a group
     used = []
     real = hostio._enqueue_download
     monkeypatch.setattr(hostio, "_enqueue_download",

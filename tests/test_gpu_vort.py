@@ -457,8 +457,8 @@ def test_lazy_4d_fields_walk_groups_of_time_steps(monkeypatch):
         return real(self, arrays)
 
     monkeypatch.setattr(hostio.Uploader, "submit", counting)
-    monkeypatch.setattr(derived, "_HOST_PIPELINE_ELEMS", 100)
-    monkeypatch.setattr(derived, "_HOST_GROUP_ELEMS", 2 * 125)  # two time steps a group
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 100)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 2 * 125)  # two time steps a group
     d = dset3.copy()
     lazy_u, lazy_v = CountingLazy(dset3.uo.values), MaskedLazy(dset3.vo.values)
     d["uo"] = DataArray(lazy_u, dset3.uo.dims)

@@ -119,10 +119,9 @@ def test_large_host_arrays_are_chunked(monkeypatch):
     broadcast along the leading axis, python-float pressures and float32-throughout results
     (numpy's promotion) included."""
     from momlevel_amd import hostio
-    from momlevel_amd.eos import _dispatch
 
-    monkeypatch.setattr(_dispatch, "_HOST_PIPELINE_ELEMS", 1000)
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 1000)
+    monkeypatch.setattr(hostio, "PIPELINE_ELEMS", 1000)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 1000)
     r = np.random.default_rng(5)
     T = r.uniform(-2, 32, (7, 5, 6, 10))
     S = r.uniform(30, 40, (7, 5, 6, 10))
@@ -136,7 +135,7 @@ def test_large_host_arrays_are_chunked(monkeypatch):
     real = hostio._enqueue_download
     monkeypatch.setattr(hostio, "_enqueue_download",
                         lambda out, dev, *a: used.append(out.nbytes) or real(out, dev, *a))
-    monkeypatch.setattr(_dispatch, "_HOST_CHUNK_ELEMS", 200_000)
+    monkeypatch.setattr(hostio, "PIECE_ELEMS", 200_000)
     T = r.uniform(-2, 32, (6, 40, 50, 60))
     S = r.uniform(30, 40, (6, 40, 50, 60))
     pz = np.linspace(1e5, 5e7, 40)[:, None, None]

@@ -804,3 +804,46 @@ def test_pending_download_is_drained_and_the_bodys_error_kept():
             twins["pending"] = stub
             raise KeyboardInterrupt
     assert [c[0] for c in stub.calls] == ["drain"]
+
+
+# ---- the host row pipeline's two pure rules (hostio.wants_pipeline / row_bounds) and is_lazy ------
+def test_wants_pipeline_needs_rows_and_more_than_the_limit():
+    from momlevel_amd import hostio
+
+    assert not hostio.wants_pipeline(1, 1 << 40)  # one leading row: nothing to group, however large
+    assert not hostio.wants_pipeline(0, 1 << 40)
+    assert not hostio.wants_pipeline(8, hostio.PIPELINE_ELEMS)
+    assert hostio.wants_pipeline(8, hostio.PIPELINE_ELEMS + 1)
+    assert hostio.wants_pipeline(2, hostio.PIPELINE_ELEMS + 1)
+    assert (hostio.PIPELINE_ELEMS, hostio.PIECE_ELEMS) == (1 << 26, 1 << 25)
+
+
+def test_row_bounds_cover_the_leading_rows():
+    from momlevel_amd import hostio
+
+    assert hostio.row_bounds(7, hostio.PIECE_ELEMS // 2) == [(0, 2), (2, 4), (4, 6), (6, 7)]
+    assert hostio.row_bounds(5, hostio.PIECE_ELEMS + 1) == [(i, i + 1) for i in range(5)]  # a row at least
+    assert hostio.row_bounds(5, 1) == [(0, 5)]
+    for nlead, per_row in ((3, 0), (0, 5), (0, 0), (7, hostio.PIECE_ELEMS // 3), (1, 1 << 40)):
+        bounds = hostio.row_bounds(nlead, per_row)
+        assert [i for i0, i1 in bounds for i in range(i0, i1)] == list(range(nlead))
+        assert all(i1 > i0 for i0, i1 in bounds)
+    assert hostio.row_bounds(3, 0) == [(0, 3)] and hostio.row_bounds(0, 5) == []
+
+
+def test_is_lazy_is_for_sliceable_sources_only():
+    import torch
+
+    from lazy_array import CountingLazy, MaskedLazy
+    from momlevel_amd import labeled
+
+    a = np.arange(6.0).reshape(2, 3)
+    for x in (np.float64(1), np.float32(1), np.int16(1), True, 1, 1.0, [1.0, 2.0], (1.0, 2.0), [], (),
+              torch.zeros(3), a, np.ma.masked_array(a), None, "abc"):
+        assert not labeled.is_lazy(x), type(x)
+    assert labeled.is_lazy(CountingLazy(a)) and labeled.is_lazy(MaskedLazy(a))
+    # one definition: the EOS front end and spice use it, under its own name
+    from momlevel_amd.eos import _dispatch
+    from momlevel_amd.spice import flament
+    assert _dispatch.is_lazy is labeled.is_lazy and flament.is_lazy is labeled.is_lazy
+    assert not hasattr(_dispatch, "_is_lazy")

@@ -201,3 +201,9 @@ def test_the_host_pipeline_takes_its_kernel():
     from momlevel_amd.spice import flament
     assert "_dispatch._host_pipeline(" in inspect.getsource(flament.spice)
     assert "Uploader" not in inspect.getsource(flament)
+    # ... and that evaluator is a caller of the one loop, which takes ITS kernel as an argument too
+    from momlevel_amd import hostio
+    assert "hostio.pipeline_rows(" in inspect.getsource(_dispatch._host_pipeline)
+    assert "Uploader" not in inspect.getsource(_dispatch)
+    assert list(inspect.signature(hostio.pipeline_rows).parameters) == [
+        "bounds", "device", "stage", "kernel", "out"]
