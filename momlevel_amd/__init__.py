@@ -28,6 +28,11 @@ staggered grid, one pass each, consuming the N^2 of ``calc_n2`` and the wave spe
 reduce a ``(..., yh, xh)`` record to its area-weighted global or per-basin means and to the
 anomalies from them -- the first thing done with a local steric field -- where the record lives.
 
+``steric_layers``, ``derived.calc_layer_integral`` and ``derived.calc_heat_content`` (EXTENSIONS as
+well) split the local steric height, any ``(..., z, yh, xh)`` field or the heat content into depth
+layers -- the upper 700 m, 700-2000 m, below -- with ``calc_dz``'s own partial cells, on a kernel that
+runs behind K2 on a device scratch of ``delta_rho`` (include/momlevel_layer.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -51,7 +56,7 @@ from . import util
 from ._lib import MomlevelHipError
 from .dynamic import inverse_barometer
 from .labeled import DataArray, Dataset
-from .steric import halosteric, steric, steric_variants, thermosteric
+from .steric import halosteric, steric, steric_layers, steric_variants, thermosteric
 
 # the reference keeps generate_test_data_time in its test_data module; the version with the
 # ``frequency`` argument ("MS" | "D") lives in timeseries_data and is published there
@@ -73,6 +78,7 @@ __all__ = [
     "regional",
     "spice",
     "steric",
+    "steric_layers",
     "steric_variants",
     "test_data",
     "thermosteric",

@@ -46,6 +46,8 @@ VORT_TILE_LANES, VORT_TILE_H, VORT_TILE_BANDS = 64, 16, 4
 # ---- constants mirrored from include/momlevel_area.h -------------------------------
 AREA_MAX_SLOTS = 16
 AREA_WINDOW = 32
+# ---- constants mirrored from include/momlevel_layer.h ------------------------------
+LAYER_MAX = 8
 
 
 def flag_tchunk(steps):
@@ -191,6 +193,15 @@ AREA_SIGNATURES = {
 }
 
 
+# The depth-layer sums (include/momlevel_layer.h): bound by load_layer() on first use, for the same
+# reason.
+LAYER_SIGNATURES = {
+    "mlx_layer_steps": (_int, []),
+    "mlx_layer_integral": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _dbl,
+                                  _vp, _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -253,11 +264,13 @@ _GROUPS = {
     "spice": (SPICE_SIGNATURES, "the spiciness kernel"),
     "vort": (VORT_SIGNATURES, "the vorticity kernels"),
     "area": (AREA_SIGNATURES, "the area-mean kernels"),
+    "layer": (LAYER_SIGNATURES, "the layer-integral kernel"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
+_layer_bound = False
 
 
 def _load_group(group):
@@ -293,6 +306,10 @@ def load_vort():
 
 def load_area():
     return _load_group("area")
+
+
+def load_layer():
+    return _load_group("layer")
 
 
 def last_error():

@@ -1262,6 +1262,67 @@ def area_anomaly(v, mean, slot=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# depth-layer sums (include/momlevel_layer.h; csrc/momlevel_layer.hip)
+# ---------------------------------------------------------------------------------------
+LAYER_MAX = _lib.LAYER_MAX  # layers per launch of layer_integral
+
+
+def __getattr__(name):
+    # LAYER_STEPS is the kernel's own constant: asked of the library on first use, so that
+    # importing this module does not need the library
+    if name == "LAYER_STEPS":
+        return int(_lib.load_layer().mlx_layer_steps())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def layer_groups(nlayers, cap=LAYER_MAX):
+    """``[(start, count)]``: the layers in launches of at most ``cap`` (as regional.slot_groups)"""
+    return [(s, min(cap, nlayers - s)) for s in range(0, nlayers, cap)]
+
+
+def layer_integral(x, z_i, depth, tops, bottoms, surface=None, scale=1.0, out=None):
+    """Depth-layer sums (mlx_layer_integral): ``out[r, l, c] = scale * sum_z calc_dz(top[l],
+    bottom[l])[z, c] * x[r, z, c]``, NaN terms skipped, z ascending, as tests/layer_numpy.py.
+
+    ``x`` (nrec, nz, plane) contiguous float32 / float64 device tensor; ``z_i`` the nz+1 interfaces;
+    ``depth`` (plane), NaN = land; ``tops`` / ``bottoms`` host sequences of equal length, a bottom
+    of +inf (or None) meaning the sea floor; ``surface`` None or (plane): NaN there gives NaN.
+    Returns (nrec, nl, plane) float64 (``out`` when given).  More than LAYER_MAX layers run as
+    several launches over groups of layers; every layer gets the bits it would get alone."""
+    require_device()
+    lib = _lib.load_layer()
+    xdt = _float_code(x, "x", 3)
+    nrec, nz, plane = (int(n) for n in x.shape)
+    dev = x.device
+    tops = np.ascontiguousarray(tops, dtype=np.float64).reshape(-1)
+    bottoms = np.ascontiguousarray(
+        [np.inf if b is None else b for b in np.asarray(bottoms, dtype=object).reshape(-1)],
+        dtype=np.float64)
+    nl = int(tops.size)
+    if nl < 1 or bottoms.size != nl:
+        raise ValueError("tops and bottoms must hold the same number (>= 1) of layers")
+    z_i = _f64(z_i, dev).reshape(-1)
+    depth = _f64(depth, dev).reshape(-1)
+    if z_i.numel() != nz + 1 or depth.numel() != plane:
+        raise ValueError(f"z_i must have nz+1 = {nz + 1} entries and depth {plane} cells")
+    if surface is not None:
+        surface = _f64(surface, dev).reshape(-1)
+        if surface.numel() != plane:
+            raise ValueError(f"surface must hold {plane} cells")
+    out = _out_like(out, (nrec, nl, plane), torch.float64, dev, "float64")
+    groups = layer_groups(nl)
+    for start, count in groups:
+        part = out if len(groups) == 1 else torch.empty((nrec, count, plane), dtype=torch.float64,
+                                                        device=dev)
+        t, b = tops[start:start + count].copy(), bottoms[start:start + count].copy()
+        _call(lib, "mlx_layer_integral", dev, _ptr(x), xdt, nrec, nz, plane, _ptr(z_i), _ptr(depth),
+              t.ctypes.data, b.ctypes.data, count, _ptr(surface), float(scale), _ptr(part))
+        if part is not out:
+            out[:, start:start + count] = part
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

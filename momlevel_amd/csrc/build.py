@@ -27,6 +27,7 @@ FEATURES = {
     "spice": ["mlx_internal.hpp", "include/momlevel_spice.h"],
     "vort": ["mlx_internal.hpp", "include/momlevel_vort.h"],
     "area": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_area.h"],
+    "layer": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_layer.h"],
 }
 
 
@@ -123,6 +124,11 @@ def vort_source_sha():
 def area_source_sha():
     """the area-mean kernels' own guard: csrc/momlevel_area.hip (+ what it includes, + flags)"""
     return feature_source_sha("area")
+
+
+def layer_source_sha():
+    """the layer-integral kernel's own guard: csrc/momlevel_layer.hip (+ what it includes, + flags)"""
+    return feature_source_sha("layer")
 
 
 def hipcc():

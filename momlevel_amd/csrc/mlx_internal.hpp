@@ -9,4 +9,22 @@ __attribute__((visibility("hidden"))) int fail(int code, const char* msg);
 // 0 for hipSuccess; otherwise records "<what>: <hip error string>" and returns the hipError_t
 __attribute__((visibility("hidden"))) int hip_status(hipError_t e, const char* what);
 }  // namespace detail
+
+// calc_dz's arithmetic for one cell and level (derived.py:295-318, fraction=False): the thickness
+// of the part of the level [ztop, zbot] that lies below `top` and above `d`, where d is the sea
+// floor after fillna(0.0) and, with a bottom, np.minimum(depth, bottom).  The ONE definition for
+// K2's default dz (top = 0, no bottom), k_calc_dz and the layer integral (momlevel_layer.hip), so
+// that their bits cannot drift.  NANS: np.minimum's NaN propagation, for callers whose d or top
+// may be NaN (k_calc_dz: a NaN top / bottom is the caller's); without it the selects are K2's.
+template <bool NANS>
+__device__ __forceinline__ double calc_dz_cell(double d, double ztop, double zbot, double top) {
+  const double dz_field = zbot - ztop;
+  double part = d - ztop;
+  part = (part < 0.0) ? 0.0 : part;
+  double result = ((NANS && part != part) || part < dz_field) ? part : dz_field;  // np.minimum
+  part = zbot - top;
+  part = (part < 0.0) ? 0.0 : part;
+  result = ((NANS && part != part) || part < result) ? part : result;
+  return result;
+}
 }  // namespace mlx

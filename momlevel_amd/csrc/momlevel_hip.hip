@@ -777,19 +777,6 @@ __global__ __launch_bounds__(kBlock) void k_fold_mask(const double* __restrict__
     out[i] = is_nan(vol0[i]) ? canonical_nan() : rho0[i];
 }
 
-// calc_dz's default-argument core, derived.py:295-318 with top=0, bottom=None
-__device__ __forceinline__ double dz_default(double depth, double ztop, double zbot) {
-  const double d = is_nan(depth) ? 0.0 : depth;  // fillna(0.0)
-  const double dz_field = zbot - ztop;
-  double part = d - ztop;
-  part = (part < 0.0) ? 0.0 : part;
-  double result = (part < dz_field) ? part : dz_field;  // np.minimum (no NaN possible here)
-  part = zbot - 0.0;
-  part = (part < 0.0) ? 0.0 : part;
-  result = (part < result) ? part : result;
-  return result;
-}
-
 // ------------------------------------------------------------------------------------
 // K2: fused EOS + delta_rho + dz-weighted column integral.
 //
@@ -897,7 +884,8 @@ __global__ __launch_bounds__(kBlock) void k_steric_local(
     } else {
       const double ztop = z_i[z], zbot = z_i[z + 1];
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) dzv.v[k] = dz_default(depth.v[k], ztop, zbot);
+      for (int k = 0; k < VEC; ++k)  // calc_dz's defaults: fillna(0.0), top = 0, no bottom (no NaN)
+        dzv.v[k] = calc_dz_cell<false>(is_nan(depth.v[k]) ? 0.0 : depth.v[k], ztop, zbot, 0.0);
     }
     if ((!GENERIC && !P3D) || p_mode == MLX_P_ZPROF) pz = p[z];
     Pack<double, VEC> pfull;
@@ -1109,12 +1097,7 @@ __global__ __launch_bounds__(kBlock) void k_calc_dz(const double* __restrict__ z
   for (int64_t z = 0; z < nz; ++z) {
     const double ztop = z_i[z], zbot = z_i[z + 1];
     const double dz_field = zbot - ztop;
-    double part = d - ztop;
-    part = (part < 0.0) ? 0.0 : part;
-    double result = (is_nan(part) || part < dz_field) ? part : dz_field;
-    part = zbot - top;
-    part = (part < 0.0) ? 0.0 : part;
-    result = (is_nan(part) || part < result) ? part : result;
+    double result = calc_dz_cell<true>(d, ztop, zbot, top);
     if (fraction) {
       const double f = (dz_field == 0.0) ? canonical_nan() : dz_field;
       const double g = (result == 0.0) ? canonical_nan() : result;

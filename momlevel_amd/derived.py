@@ -19,6 +19,7 @@ import torch
 from . import core, engine, hostio, spice, util
 from .adapters import accepts_xarray
 from .labeled import DataArray, check_field_dtype, is_lazy
+from .steric import OHC_CP
 
 __all__ = [
     "adjust_negative_n2",
@@ -26,6 +27,8 @@ __all__ = [
     "calc_beta",
     "calc_coriolis",
     "calc_dz",
+    "calc_heat_content",
+    "calc_layer_integral",
     "calc_masso",
     "calc_n2",
     "calc_pdens",
@@ -38,6 +41,7 @@ __all__ = [
     "calc_stability_angle",
     "calc_volo",
     "calc_wave_speed",
+    "layer_bounds",
 ]
 
 
@@ -722,3 +726,180 @@ def calc_rossby_rd(wave_speed, coriolis):
     return DataArray(out if on_device else hostio.to_host(out), wave_speed.dims,
                      {k: v for k, v in coords.items() if set(v.dims) <= set(wave_speed.dims)},
                      {"long name": "Rossby radius of deformation", "units": "m"}, None)
+
+
+# ---------------------------------------------------------------------------------------
+# depth-layer sums (EXTENSION; csrc/momlevel_layer.hip)
+# ---------------------------------------------------------------------------------------
+def layer_bounds(layers):
+    """The public spelling of depth layers -> ``(tops, bottoms)`` float64 arrays, a bottom of +inf
+    meaning the sea floor.  Two spellings: a sequence of ``(top, bottom)`` pairs in the units of
+    ``depth`` (``bottom=None``: the sea floor; pairs may overlap -- ``(0, 700)`` beside
+    ``(0, 2000)``), or a flat sequence of edges ``[0, 700, 2000, None]``: consecutive layers.
+    ``ValueError`` for negative or NaN bounds, ``bottom <= top``, a ``None`` anywhere but a last
+    bottom, and an empty list."""
+    items = list(layers) if layers is not None else []
+    if not items:
+        raise ValueError("layers is empty")
+
+    def is_pair(item):
+        return (not isinstance(item, (str, bytes)) and item is not None and np.ndim(item) == 1
+                and len(item) == 2)
+
+    if all(is_pair(item) for item in items):
+        pairs = [(item[0], item[1]) for item in items]
+    elif all(item is None or np.ndim(item) == 0 for item in items):
+        if len(items) < 2:
+            raise ValueError("a list of edges needs two entries at least")
+        if any(e is None for e in items[:-1]):
+            raise ValueError("None (the sea floor) can only be the last edge")
+        pairs = list(zip(items[:-1], items[1:]))
+    else:
+        raise ValueError("layers must be (top, bottom) pairs or a flat sequence of edges")
+    tops = np.empty(len(pairs), dtype=np.float64)
+    bottoms = np.empty(len(pairs), dtype=np.float64)
+    for l, (top, bottom) in enumerate(pairs):
+        if top is None:
+            raise ValueError(f"layer {l}: None (the sea floor) can only be a bottom")
+        top = float(top)
+        bottom = np.inf if bottom is None else float(bottom)
+        if np.isnan(top) or np.isnan(bottom):
+            raise ValueError(f"layer {l}: a bound is NaN")
+        if top < 0 or bottom < 0:
+            raise ValueError(f"layer {l}: bounds must not be negative")
+        if bottom <= top:
+            raise ValueError(f"layer {l}: bottom {bottom} is not below top {top}")
+        tops[l], bottoms[l] = top, bottom
+    return tops, bottoms
+
+
+def _check_layers_in_cells(tops, bottoms, z_i):
+    """calc_dz gives min(zbot - top, bottom - ztop), not bottom - top, where top and bottom both
+    lie strictly inside ONE model cell (derived.py:311-318): refused, certainly not what was meant"""
+    z = np.asarray(z_i, dtype=np.float64).reshape(-1)
+    for l, (top, bottom) in enumerate(zip(tops, bottoms)):
+        inside = (z[:-1] < top) & (top < z[1:]) & (z[:-1] < bottom) & (bottom < z[1:])
+        if np.any(inside):
+            k = int(np.argmax(inside))
+            raise ValueError(f"layer {l} ({top}, {bottom}) lies strictly inside one model cell "
+                             f"({z[k]}, {z[k + 1]}): calc_dz does not give bottom - top there")
+
+
+def _layer_coords(tops, bottoms):
+    nl = len(tops)
+    return {
+        "layer": DataArray(np.arange(nl, dtype=np.int64), ("layer",), None, None, "layer"),
+        "layer_top": DataArray(np.asarray(tops, dtype=np.float64).copy(), ("layer",), None,
+                               {"long_name": "Top of the depth layer"}, "layer_top"),
+        "layer_bottom": DataArray(np.where(np.isinf(bottoms), np.nan, bottoms), ("layer",), None,
+                                  {"long_name": "Bottom of the depth layer (NaN: the sea floor)"},
+                                  "layer_bottom"),
+    }
+
+
+@accepts_xarray
+def calc_layer_integral(field, interfaces, depth, layers, zcoord="z_l", scale=1.0, wet=None):
+    """EXTENSION (not in momlevel): ``scale * (calc_dz(top, bottom) * field).sum(zcoord)`` for
+    every depth layer of ``layers`` (see layer_bounds), NaN terms skipped, in one pass over the
+    field -- the specification is the numpy restatement tests/layer_numpy.py.
+
+    ``field``: a float32 / float64 DataArray (not a Dataset) with ``zcoord`` and the two horizontal
+    dims of ``depth`` right behind it, any dims before; ``interfaces``: the nz+1 interface depths;
+    ``depth`` ``(y, x)``, NaN = land (contributes 0); ``wet``: an optional ``(y, x)`` array, the
+    result is NaN where it is NaN.  Returns float64 with dims ``lead... + ("layer", y, x)`` and the
+    coordinates ``layer`` (0 .. nl-1), ``layer_top`` and ``layer_bottom`` (NaN: the sea floor).
+    Device input gives device output; a large host or lazy field goes up in groups of whole
+    leading rows and is never materialised whole.
+
+    The layer thickness per cell is calc_dz's, bit for bit.  A layer whose top and bottom both lie
+    strictly inside one model cell is a ``ValueError``: calc_dz returns
+    ``min(zbot - top, bottom - ztop)`` there, not ``bottom - top``.  Where the SEA FLOOR and ``top``
+    cut the same cell calc_dz does the same (``min(zbot - top, depth - ztop)``); that depends on
+    the cell and cannot be refused -- parity with calc_dz is the contract."""
+    if not isinstance(field, DataArray):
+        raise TypeError("field must be a DataArray (a Dataset is not accepted)")
+    float_name(field, "field")
+    tops, bottoms = layer_bounds(layers)
+    if not isinstance(depth, DataArray):
+        depth = DataArray(depth)
+    if depth.ndim != 2:
+        raise ValueError(f"depth has dims {depth.dims}: a 2-D (y, x) field is expected")
+    zi, nrec, nz, plane = _z_layout(field, zcoord)
+    hdims, hshape = tuple(field.dims[zi + 1:]), tuple(int(n) for n in field.shape[zi + 1:])
+    if len(hdims) != 2 or hshape != tuple(int(n) for n in depth.shape):
+        raise ValueError(f"the field's dims behind {zcoord!r} are {hdims}{hshape}: expected depth's "
+                         f"plane {tuple(depth.shape)}")
+    z_i = np.asarray(interfaces.values if isinstance(interfaces, DataArray) else interfaces,
+                     dtype=np.float64).reshape(-1)
+    if z_i.size != nz + 1:
+        raise ValueError(f"interfaces holds {z_i.size} values: {nz + 1} expected")
+    depth_np = np.asarray(depth.values, dtype=np.float64)
+    # calc_dz's sign checks stay on the host (derived.py:284-292)
+    assert bool(np.all(np.nan_to_num(depth_np, nan=0.0) >= 0)), (
+        "Depth values must all be positive-definite"
+    )
+    if zcoord in field.coords:
+        assert bool(np.all(np.asarray(field.coords[zcoord].values) >= 0)), (
+            "Vertical coordinate levels must all be positive-definite"
+        )
+    assert bool(np.all(z_i >= 0)), "Vertical coordinate interfaces must all be positive-definite"
+    _check_layers_in_cells(tops, bottoms, z_i)
+    if wet is not None:
+        wet = wet.data if isinstance(wet, DataArray) else wet
+        if tuple(int(n) for n in wet.shape) != hshape:
+            raise ValueError(f"wet {tuple(wet.shape)} does not cover the plane {hshape}")
+
+    dev = engine.device_of(field.data, depth.data)
+    on_device = field.is_device
+    tdt = torch.float32 if str(field.dtype) == "float32" else torch.float64
+    z_d = engine.to_device(z_i, dev, torch.float64)
+    depth_d = engine.to_device(depth.data, dev, torch.float64).contiguous().reshape(-1)
+    wet_d = None if wet is None else engine.to_device(wet, dev, torch.float64).contiguous().reshape(-1)
+    nl = len(tops)
+    lead = tuple(int(n) for n in field.shape[:zi])
+    shape = lead + (nl,) + hshape
+
+    def integral(x, n):
+        return core.layer_integral(x.to(tdt).reshape(n, nz, plane), z_d, depth_d, tops, bottoms,
+                                   surface=wet_d, scale=scale)
+
+    if not on_device and len(lead) >= 1 and hostio.wants_pipeline(lead[0], nrec * nz * plane):
+        # a record's layers depend on that record alone: the grouping cannot show in the result
+        inner = nrec // lead[0]
+        source = field.data if field.is_lazy else field.values
+        out = hostio.pipeline_rows(
+            hostio.row_bounds(lead[0], inner * nz * plane), dev, hostio.leading_slices([source]),
+            lambda tensors, i0, i1: integral(tensors[0], (i1 - i0) * inner),
+            np.empty(shape, dtype=np.float64))
+    else:
+        x = field.data if on_device else engine.to_device(field.values, dev, tdt)
+        out = integral(x.contiguous(), nrec).reshape(shape)
+        if not on_device:
+            out = hostio.to_host(out)
+    coords = {k: c for k, c in field.coords.items() if zcoord not in c.dims}
+    coords.update(_layer_coords(tops, bottoms))
+    return DataArray(out, tuple(field.dims[:zi]) + ("layer",) + hdims, coords, None, field.name)
+
+
+@accepts_xarray
+def calc_heat_content(thetao, interfaces, depth, layers=None, rhozero=1035.0, cp=OHC_CP,
+                      zcoord="z_l", wet=None):
+    """EXTENSION (not in momlevel): ocean heat content per unit area and depth layer relative to
+    0 degC, ``rhozero * cp * sum_z(thetao * dz_l)`` in J m-2: calc_layer_integral with
+    ``scale = float64(rhozero) * float64(cp)``.  ``layers=None`` is the whole column and the result
+    has no ``layer`` dim."""
+    whole = layers is None
+    scale = float(np.float64(rhozero) * np.float64(cp))
+    out = calc_layer_integral(thetao, interfaces, depth, [(0.0, None)] if whole else layers,
+                              zcoord=zcoord, scale=scale, wet=wet)
+    if whole:
+        ax = out.dims.index("layer")
+        data = out.data.reshape(out.shape[:ax] + out.shape[ax + 1:])
+        coords = {k: c for k, c in out.coords.items() if "layer" not in c.dims}
+        out = DataArray(data, out.dims[:ax] + out.dims[ax + 1:], coords, None, out.name)
+    out.attrs.update({
+        "long_name": "Ocean heat content per unit area relative to 0 degC (momlevel_amd extension)",
+        "units": "J m-2",
+        "comment": f"rhozero={rhozero} kg m-3 * cp={cp} J kg-1 K-1 * sum_z(thetao*dz)",
+    })
+    return out

@@ -550,3 +550,78 @@ def local_steric_variants(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, z_i
     if drho32 and annual:  # the float64 means (1/12 of the record) are complete here: narrow them
         drho = {v: _narrowed(d) for v, d in drho.items()}
     return {v: (drho[v], eta[v]) for v in variants}
+
+
+def local_steric_layers(T, S, T0, S0, rho0, vol0, pres, rhozero, variants, tops, bottoms, z_i,
+                        deptho, eos="wright", f32_mode="faithful", out_host=None, steps=None,
+                        reference_is_step0=False):
+    """{variant: (eta (nt, ny, nx), eta_layers (nt, nl, ny, nx))} -- an EXTENSION: K2's height
+    field and, behind it, its split into the depth layers ``(tops[l], bottoms[l])``
+    (core.layer_integral with ``surface = vol0[0]`` and ``scale = -1/rhozero``), chunk by chunk.
+
+    Per time chunk K2 writes its float64 delta_rho into a DEVICE SCRATCH of the chunk's size, the
+    layer kernel reads it there, and only eta and the ``nl`` layer planes per step go to the
+    result: delta_rho never leaves the device.  ``eta`` is bit for bit local_steric_variants'.
+    Device-resident inputs are chunked too (a whole record's delta_rho would not fit beside them)
+    and give device tensors; host inputs give host arrays (``out_host``: as there)."""
+    dev, pres, out_host, (rho0m, surface, neg_inv), depth = _local_operands(
+        T, S, rho0, vol0, pres, rhozero, z_i, deptho, None, out_host)
+    T0 = to_device(T0, dev, _stream_dtype(T0))
+    S0 = to_device(S0, dev, _stream_dtype(S0))
+    nz, ny, nx = tuple(rho0m.shape)
+    plane = ny * nx
+    nt = T.shape[0]
+    nl = len(tops)
+    depth_flat = depth["deptho"].contiguous().reshape(-1)
+    rows = core.LOCAL_DECOMP_ROWS
+    one_pass = (set(variants) == set(rows) and len(variants) == 3 and T.ndim == 4 and S.ndim == 4
+                and _reference_matches(T, S, T0, S0))
+    nscratch = 3 if one_pass else 1
+    # the scratch delta_rho of a step, and what a step's results hold on the device on their way out
+    extra = nscratch * nz * plane * 8 + len(variants) * (nl + 1) * plane * 8
+    extra += _pressure_bytes_per_step(pres)
+    Ts, Ss = _streamed_pair(variants, T, S, T0, S0)
+    # (device-resident fields are chunked by the same rule: TimeChunks sizes the steps from `extra`)
+    chunks = TimeChunks(Ts, Ss, dev, steps=steps, extra_bytes_per_step=extra, ramp=out_host,
+                        first_step=(T0, S0) if reference_is_step0 else None)
+    cs = chunks.steps
+    scratch = torch.empty((nscratch, cs, nz, ny, nx), dtype=torch.float64, device=dev)
+
+    def alloc(shape):
+        return _host_output(shape) if out_host else torch.empty(shape, dtype=torch.float64, device=dev)
+
+    eta = {v: alloc((nt, ny, nx)) for v in variants}
+    lay = {v: alloc((nt, nl, ny, nx)) for v in variants}
+    kw = dict(depth, eos=eos, f32_mode=f32_mode, want_delta_rho=True,
+              delta_rho_dtype=torch.float64)
+
+    def layers_of(d, n, out=None):
+        return core.layer_integral(d.reshape(n, nz, plane), depth["z_i"], depth_flat, tops, bottoms,
+                                   surface=surface, scale=neg_inv, out=out)
+
+    with (hostio.Downloader(dev) if out_host else contextlib.nullcontext()) as results:
+        for t0, t1, Tc, Sc in chunks:
+            n = t1 - t0
+            pc = pressure_chunk(pres, t0, t1, dev)
+            going_out = []
+            if one_pass:
+                e3 = torch.empty((3, n, ny, nx), dtype=torch.float64, device=dev)
+                core.steric_local_decomp(Tc, Sc, T0, S0, rho0m, surface, pc, neg_inv,
+                                         delta_rho_out=scratch[:, :n], eta_out=e3, **kw)
+            for v in variants:
+                if one_pass:
+                    d, e = scratch[rows.index(v), :n], e3[rows.index(v)]
+                    if not out_host:
+                        eta[v][t0:t1] = e
+                else:
+                    Tv, Sv = _variant_operands(v, Tc, Sc, T0, S0)
+                    d = scratch[0, :n]
+                    _, e = core.steric_local(Tv, Sv, rho0m, surface, pc, neg_inv, delta_rho_out=d,
+                                             eta_out=None if out_host else eta[v][t0:t1], **kw)
+                if out_host:
+                    going_out += [(eta[v][t0:t1], e), (lay[v][t0:t1], layers_of(d, n))]
+                else:
+                    layers_of(d, n, out=lay[v][t0:t1].reshape(n, nl, plane))
+            if going_out:
+                results.submit(going_out)
+    return {v: (eta[v], lay[v]) for v in variants}

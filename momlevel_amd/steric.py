@@ -40,7 +40,7 @@ from .util import (
     validate_dataset,
 )
 
-__all__ = ["halosteric", "steric", "steric_variants", "thermosteric"]
+__all__ = ["halosteric", "steric", "steric_layers", "steric_variants", "thermosteric"]
 
 _VARIANTS = ("steric", "thermosteric", "halosteric")
 
@@ -203,6 +203,41 @@ def _local_results(ops, dset, rho0, variants, dtype, rhozero, names, cdims3, coo
     return out
 
 
+def _layer_results(ops, dset, rho0, variants, dtype, rhozero, names, cdims3, coords_for, layers,
+                   reference_is_step0=False):
+    """EXTENSION: the height field of _local_results and its split into depth layers
+    (engine.local_steric_layers); ``layers``: the (tops, bottoms) of derived.layer_bounds.  No
+    delta_rho in the result: the field stays on the device, in a scratch of one time chunk."""
+    from . import derived
+
+    T, S, T0, S0, vol0, p, eos = ops
+    tcoord, zcoord, zbounds = names
+    hdims = cdims3[1:]
+    deptho = dset["deptho"].transpose(*hdims)
+    _check_dz_inputs(dset[zcoord], dset[zbounds], deptho)
+    tops, bottoms = layers
+    derived._check_layers_in_cells(tops, bottoms, dset[zbounds].values)
+    fields = engine.local_steric_layers(
+        T, S, T0, S0, rho0, vol0, p, rhozero, variants, tops, bottoms,
+        z_i=dset[zbounds].data, deptho=deptho.data, eos=eos, f32_mode=_f32_mode(),
+        reference_is_step0=reference_is_step0,
+    )
+    out = {}
+    for v in variants:
+        sealevel, by_layer = fields[v]
+        result = Dataset()
+        result[v] = DataArray(sealevel, (tcoord,) + hdims, coords_for((tcoord,) + hdims))
+        ldims = (tcoord, "layer") + hdims
+        coords = coords_for(ldims)
+        coords.update(derived._layer_coords(tops, bottoms))
+        result[v + "_layers"] = DataArray(
+            by_layer, ldims, coords,
+            {"long_name": f"{v.capitalize()} height adjustment by depth layer", "units": "m"})
+        result[v + "_layers"].encoding["dtype"] = dtype
+        out[v] = result
+    return out
+
+
 def all_ranks_ok(exchange, error=None):
     """Make a rank-local failure COLLECTIVE (tiled multi-GPU runs): one tiny all-reduce of an error
     flag, after which either every rank goes on or every rank raises -- the failing rank its own
@@ -270,7 +305,7 @@ def _steric_many(*args, **kwargs):
 
 def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rhozero, patm,
                  equation_of_state, domain, dtype, strict, annual, verbose, heat_cp=None,
-                 exchange=None, delta_rho_dtype=None):
+                 exchange=None, delta_rho_dtype=None, layers=None):
     """The body of steric() for one or several variants sharing one reference state and one
     pass of theta/S through the device.  Returns ({variant: result}, reference).
     ``twins``: the caller's dict for the device tensors of a self-made reference state (and its
@@ -278,7 +313,10 @@ def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rho
     ``exchange``: None, or -- when ``dset`` is ONE RANK'S horizontal tile of a multi-GPU run
     (momlevel_amd.parallel.steric) -- a callable summing a float64 vector over the ranks; the
     global sums (sum of areacello, volo, masso) then go through it, everything else is local.
-    ``delta_rho_dtype``: see delta_rho_dtype_for (None: the environment decides)."""
+    ``delta_rho_dtype``: see delta_rho_dtype_for (None: the environment decides).
+    ``layers`` (steric_layers; local domain, no annual means): the (tops, bottoms) of
+    derived.layer_bounds -- the results then hold the height field and its split into those depth
+    layers instead of delta_rho (_layer_results).  None changes nothing."""
     drho32 = delta_rho_dtype_for(dtype, delta_rho_dtype) == "float32"  # (refuses junk before any work)
     dset = dset.rename(varname_map)
     names = default_coords(coord_names)
@@ -361,6 +399,9 @@ def _steric_body(twins, dset, variants, reference, coord_names, varname_map, rho
         results = _global_results(ops, reference, variants, dtype, tcoord, coords_for, deferred,
                                   heat=None if heat_cp is None else (rhozero, heat_cp),
                                   exchange=exchange, area_total=area_total)
+    elif layers is not None:
+        results = _layer_results(ops, dset, slab("rho"), variants, dtype, rhozero, names, cdims3,
+                                 coords_for, layers, reference_is_step0="thetao" in twins)
     else:
         if heat_cp is not None:
             raise ValueError("heat_content is a global integral: use domain='global'")
@@ -485,6 +526,50 @@ def steric_variants(
         dset, tuple(variants), reference, coord_names, varname_map, rhozero, patm,
         equation_of_state, domain, dtype, strict, annual, verbose,
         heat_cp=cp if heat_content else None, delta_rho_dtype=delta_rho_dtype,
+    )
+    return (results, reference)
+
+
+@accepts_xarray
+def steric_layers(
+    dset,
+    layers,
+    variants=("steric",),
+    reference=None,
+    coord_names=None,
+    varname_map=None,
+    rhozero=1035.0,
+    patm=101325.0,
+    equation_of_state="Wright",
+    dtype="float32",
+    strict=True,
+    verbose=False,
+):
+    """EXTENSION (not in momlevel): the local steric height and its split into depth layers --
+    "how much of this rise is in the upper 700 m?" -- without ``delta_rho`` leaving the device.
+
+    In the reference it is ``(-1/rhozero) * (calc_dz(z_l, z_i, deptho, top=top, bottom=bottom) *
+    delta_rho).sum("z_l")`` of the ``delta_rho`` that ``steric()`` returns, masked like the height
+    field; here K2 writes each time chunk's ``delta_rho`` into a device scratch and the layer
+    kernel (derived.calc_layer_integral's) sums it there.
+
+    ``layers``: ``(top, bottom)`` pairs or a list of edges such as ``[0, 700, 2000, None]``
+    (derived.layer_bounds; None: the sea floor; pairs may overlap).  A layer that lies strictly
+    inside one model cell is a ``ValueError`` (see calc_layer_integral).  Validation, reference
+    state and operand order are those of ``steric(domain="local")``.
+
+    Returns ``(results, reference)``: ``results[v]`` holds ``v`` -- dims (time, y, x), bit for bit
+    what ``steric(variant=v)`` returns -- and ``v_layers`` -- dims (time, layer, y, x), with the
+    coordinates ``layer``, ``layer_top`` and ``layer_bottom`` (NaN: the sea floor) -- both in m,
+    both with ``encoding["dtype"]``.  There is no ``delta_rho`` in the result and no ``annual``
+    argument (``util.annual_average`` of the result gives annual means); the
+    ``MOMLEVEL_AMD_DELTA_RHO*`` switches do not apply."""
+    from . import derived
+
+    bounds = derived.layer_bounds(layers)
+    results, reference = _steric_many(
+        dset, tuple(variants), reference, coord_names, varname_map, rhozero, patm,
+        equation_of_state, "local", dtype, strict, False, verbose, layers=bounds,
     )
     return (results, reference)
 
