@@ -7,7 +7,7 @@ detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
-include/momlevel_area.h).
+include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -33,6 +33,12 @@ well) split the local steric height, any ``(..., z, yh, xh)`` field or the heat 
 layers -- the upper 700 m, 700-2000 m, below -- with ``calc_dz``'s own partial cells, on a kernel that
 runs behind K2 on a device scratch of ``delta_rho`` (include/momlevel_layer.h).
 
+``filters`` (an EXTENSION too) smooths a ``(time, ...)`` record along time where it lives:
+``rolling_mean`` / ``rolling_sum`` (xarray's ``.rolling().mean()`` values), ``lowpass`` (Lanczos),
+``time_filter`` (any FIR weights) and ``rolling_trend`` (the least-squares rate over sliding windows
+against the actual time axis) are one NaN-aware banded operator along time with weight tables made
+on the host (include/momlevel_filter.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -44,6 +50,7 @@ __version__ = "0.1.0"
 from . import derived
 from . import dynamic
 from . import eos
+from . import filters
 from . import reference
 from . import regional
 from . import spice
@@ -73,6 +80,7 @@ __all__ = [
     "dynamic",
     "inverse_barometer",
     "eos",
+    "filters",
     "halosteric",
     "reference",
     "regional",

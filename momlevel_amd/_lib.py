@@ -48,6 +48,8 @@ AREA_MAX_SLOTS = 16
 AREA_WINDOW = 32
 # ---- constants mirrored from include/momlevel_layer.h ------------------------------
 LAYER_MAX = 8
+# ---- constants mirrored from include/momlevel_filter.h -----------------------------
+FILTER_NORMALISE = 1
 
 
 def flag_tchunk(steps):
@@ -202,6 +204,16 @@ LAYER_SIGNATURES = {
 }
 
 
+# The time filter (include/momlevel_filter.h): bound by load_filter() on first use, for the same
+# reason.
+FILTER_SIGNATURES = {
+    "mlx_filter_tile": (_i64, []),
+    "mlx_filter_window_edge": (_i64, [_int]),
+    "mlx_filter_apply": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _int, _i64, _i64, _vp, _int,
+                               _vp]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -265,12 +277,13 @@ _GROUPS = {
     "vort": (VORT_SIGNATURES, "the vorticity kernels"),
     "area": (AREA_SIGNATURES, "the area-mean kernels"),
     "layer": (LAYER_SIGNATURES, "the layer-integral kernel"),
+    "filter": (FILTER_SIGNATURES, "the time-filter kernel"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
-_layer_bound = False
+_layer_bound = _filter_bound = False
 
 
 def _load_group(group):
@@ -310,6 +323,10 @@ def load_area():
 
 def load_layer():
     return _load_group("layer")
+
+
+def load_filter():
+    return _load_group("filter")
 
 
 def last_error():

@@ -1323,6 +1323,84 @@ def layer_integral(x, z_i, depth, tops, bottoms, surface=None, scale=1.0, out=No
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# the time filter (include/momlevel_filter.h; csrc/momlevel_filter.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+def filter_tile():
+    """Output steps a lane of mlx_filter_apply sums together from one pass over its rows: the
+    kernel's tile along time (output tiles start at multiples of it)."""
+    return int(_lib.load_filter().mlx_filter_tile())
+
+
+def filter_window_edges():
+    """The window lengths at which the kernel's walk over a window changes, ascending
+    (mlx_filter_window_edge)."""
+    lib = _lib.load_filter()
+    edges = []
+    while True:
+        e = int(lib.mlx_filter_window_edge(len(edges)))
+        if e <= 0:
+            return tuple(edges)
+        edges.append(e)
+
+
+def filter_weights(w, nt):
+    """The host-side mirror of a weight table as the kernel reads it: float64, ``(W,)`` (one row
+    for every step) or ``(nt, W)`` (row t for output t), 1 <= W <= nt, every weight finite; or
+    ``ValueError``.  Touches no device."""
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    if w.ndim not in (1, 2) or w.shape[-1] < 1:
+        raise ValueError("weights must be (W,) or (nt, W) with W >= 1")
+    if w.ndim == 2 and w.shape[0] != int(nt):
+        raise ValueError(f"a weight table needs one row per step: ({int(nt)}, W), got {w.shape}")
+    if w.shape[-1] > int(nt):
+        raise ValueError(f"the window ({w.shape[-1]} steps) is longer than the record ({int(nt)})")
+    if not np.isfinite(w).all():
+        raise ValueError("weights must be finite")
+    return w
+
+
+def time_filter(y, w, lead, min_count=None, normalise=False, out=None, out_dtype=None):
+    """The banded linear operator along the leading axis (mlx_filter_apply):
+    ``out[t] = sum_k w[t, k] * y[t - lead + k]``, k = 0 .. W-1 ascending, in float64, as
+    tests/filter_numpy.py.  y (nt, ...) float32 / float64 on the device; ``w`` a host array ``(W,)``
+    or ``(nt, W)`` (uploaded as float64; non-finite weights are a ``ValueError``) or a float64
+    device tensor of one of those shapes (its values are the caller's); ``0 <= lead < W``.  A step
+    is valid when it lies in the record and is not NaN; fewer than ``min_count`` (default W) valid
+    steps give NaN; ``normalise`` divides by the sum of the valid steps' weights.  Returns
+    (nt, ...) of ``out_dtype`` (default y's dtype; float32 is the float64 result rounded once)."""
+    require_device()
+    lib = _lib.load_filter()
+    y, nt, n, code = _time_record(y)
+    if isinstance(w, torch.Tensor) and w.is_cuda:
+        if w.dtype != torch.float64 or w.device != y.device or not w.is_contiguous():
+            raise ValueError(f"device weights must be a contiguous float64 tensor on {y.device}")
+        wd = w
+    else:
+        wd = hostio.to_device(filter_weights(w, nt), y.device, torch.float64).contiguous()
+    if wd.dim() not in (1, 2) or (wd.dim() == 2 and wd.shape[0] != nt):
+        raise ValueError(f"weights must be (W,) or ({nt}, W)")
+    W = int(wd.shape[-1])
+    if not 1 <= W <= nt:
+        raise ValueError(f"the window must hold 1 .. {nt} steps, got {W}")
+    lead = int(lead)
+    if not 0 <= lead < W:
+        raise ValueError(f"lead must lie in [0, {W}), got {lead}")
+    min_count = W if min_count is None else int(min_count)
+    if not 1 <= min_count <= W:
+        raise ValueError(f"min_count must lie in [1, {W}], got {min_count}")
+    out_dtype = y.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"out_dtype must be float32 or float64, got {out_dtype}")
+    out = _out_like(out, tuple(y.shape), out_dtype, y.device)
+    if n == 0:
+        return out
+    _call(lib, "mlx_filter_apply", y.device, _ptr(y), code, _ptr(wd), W, W if wd.dim() == 2 else 0,
+          lead, min_count, _lib.FILTER_NORMALISE if normalise else 0, nt, n, _ptr(out),
+          DTYPE_F64 if out_dtype == torch.float64 else DTYPE_F32)
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

@@ -28,6 +28,7 @@ FEATURES = {
     "vort": ["mlx_internal.hpp", "include/momlevel_vort.h"],
     "area": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_area.h"],
     "layer": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_layer.h"],
+    "filter": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_filter.h"],
 }
 
 
@@ -129,6 +130,11 @@ def area_source_sha():
 def layer_source_sha():
     """the layer-integral kernel's own guard: csrc/momlevel_layer.hip (+ what it includes, + flags)"""
     return feature_source_sha("layer")
+
+
+def filter_source_sha():
+    """the time-filter kernel's own guard: csrc/momlevel_filter.hip (+ what it includes, + flags)"""
+    return feature_source_sha("filter")
 
 
 def hipcc():
