@@ -55,6 +55,15 @@ int64_t mlx_filter_tile(void);
  * rows are loaded in batches. */
 int64_t mlx_filter_window_edge(int i);
 
+/* Consecutive time tiles one block walks in the launch of an (nt, n) record whose lanes hold
+ * cells_per_lane cells (4, 2 or 1; the widest that divides n and that the alignment of y and out
+ * allows -- see mlx_filter_apply): ceil(ceil(nt / tile) / gy), where gy, the blocks along time, is
+ * cut down once the launch has enough blocks without them.  1 for short or narrow records.  Host
+ * arithmetic only, the rule the launch itself goes by; the results do not depend on it.  0 for
+ * extents mlx_filter_apply refuses, a cells_per_lane that is not 1, 2 or 4, or one that does not
+ * divide n. */
+int64_t mlx_filter_tiles_per_block(int64_t nt, int64_t n, int cells_per_lane);
+
 /* y: (nt, n) C-contiguous, MLX_DTYPE_F64 or MLX_DTYPE_F32 (dtype), on the device.
  * w: float64 on the device; w_stride == 0: one row (W) for every step; w_stride == W: a table
  * (nt, W), row t for output t.  1 <= W <= nt, 0 <= lead < W, 1 <= min_count <= W.

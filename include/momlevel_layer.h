@@ -58,6 +58,13 @@ extern "C" {
  * formed once and used for that many records */
 int mlx_layer_steps(void);
 
+/* Block rows along the records (gridDim.y) of a call over nrec records: min(ceil(nrec /
+ * mlx_layer_steps()), cap).  Up to the cap a block carries one group of mlx_layer_steps() records;
+ * past it a block goes on to the group cap rows further, and so on, so mlx_layer_record_blocks of
+ * a huge nrec is the cap.  Host arithmetic only, the rule the launch itself goes by; a record's
+ * bits do not depend on it.  0 for nrec <= 0 or nrec > 2^38. */
+int mlx_layer_record_blocks(int64_t nrec);
+
 /* out[r, l, c] as defined above.
  *
  *   x:       (nrec, nz, plane)  `x_dtype` (MLX_DTYPE_F64 | MLX_DTYPE_F32), device

@@ -67,6 +67,15 @@ extern "C" {
  * 0 for any other value */
 int64_t mlx_vort_tile_width(int arith_dtype);
 
+/* Records one launch of the packed path takes for a corner plane of (ny, nx) and arithmetic in
+ * `arith_dtype`: a call over more records is cut into launches of that many, each at its own
+ * offset of whole planes into the fields and the result.  0 where the shape sends the plane cell
+ * by cell (nx not a multiple of the pack, or a plane of more tiles than one grid holds), for
+ * ny or nx < 1 or ny * nx > 2^38, and for any other dtype.  (A symmetric grid or a pointer that is
+ * not aligned for its pack access also goes cell by cell; the query cannot see those.)  Host
+ * arithmetic only, the rule the launches themselves go by; a cell's bits do not depend on it. */
+int64_t mlx_vort_records_per_launch(int64_t ny, int64_t nx, int arith_dtype);
+
 /* zeta = ( -diff_y(u * dx) + diff_x(v * dy) ) / area                        derived.py:232-239
  *
  * ny, nx: the extents of the corner plane.  With s = symmetric (0 or 1):

@@ -177,6 +177,7 @@ SPICE_SIGNATURES = {
 # same reason.
 VORT_SIGNATURES = {
     "mlx_vort_tile_width": (_i64, [_int]),
+    "mlx_vort_records_per_launch": (_i64, [_i64, _i64, _int]),
     "mlx_vort_rel_vort": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _i64, _i64, _i64, _int, _vp,
                                  _vp]),
     "mlx_vort_pv": (_int, [_vp, _int, _vp, _int, _vp, _int, _i64, _i64, _i64, _int, _int, _dbl,
@@ -199,6 +200,7 @@ AREA_SIGNATURES = {
 # reason.
 LAYER_SIGNATURES = {
     "mlx_layer_steps": (_int, []),
+    "mlx_layer_record_blocks": (_int, [_i64]),
     "mlx_layer_integral": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _dbl,
                                   _vp, _vp]),
 }
@@ -209,6 +211,7 @@ LAYER_SIGNATURES = {
 FILTER_SIGNATURES = {
     "mlx_filter_tile": (_i64, []),
     "mlx_filter_window_edge": (_i64, [_int]),
+    "mlx_filter_tiles_per_block": (_i64, [_i64, _i64, _int]),
     "mlx_filter_apply": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _int, _i64, _i64, _vp, _int,
                                _vp]),
 }

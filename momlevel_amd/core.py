@@ -130,6 +130,15 @@ def _float_code(x, name, ndim=None):
     return DTYPE_F64 if x.dtype == torch.float64 else DTYPE_F32
 
 
+def _query_dtype(dtype):
+    """The dtype code of a geometry query's ``dtype`` (a torch or numpy float32 / float64)."""
+    name = str(dtype).replace("torch.", "")
+    name = name if name in ("float32", "float64") else np.dtype(dtype).name
+    if name not in ("float32", "float64"):
+        raise TypeError(f"records are float32 or float64, not {name}")
+    return DTYPE_F64 if name == "float64" else DTYPE_F32
+
+
 def _out_like(out, shape, dtype, device, noun=None):
     """``out`` when it is a contiguous ``dtype`` tensor of ``shape`` on ``device``; a new one for
     None.  ``noun``: how the error text names the dtype (default: as torch prints it)."""
@@ -1089,6 +1098,13 @@ def vort_tile():
             _lib.VORT_TILE_H, _lib.VORT_TILE_BANDS)
 
 
+def vort_records_per_launch(ny, nx, dtype=torch.float64):
+    """Records one launch of the packed path of rel_vort / potential_vorticity takes for a corner
+    plane of (ny, nx) and arithmetic in ``dtype`` (mlx_vort_records_per_launch); a call over more is
+    cut into launches of that many.  0 where the shape sends the plane cell by cell."""
+    return int(_lib.load_vort().mlx_vort_records_per_launch(int(ny), int(nx), _query_dtype(dtype)))
+
+
 def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
     """Relative vorticity on the C grid (mlx_vort_rel_vort): ``( -diff_y(u dx) + diff_x(v dy) ) /
     area`` with zero padding.  ``area`` is the (ny, nx) corner plane; with s = int(symmetric) ``u``
@@ -1191,11 +1207,7 @@ AREA_WINDOW = _lib.AREA_WINDOW  # records a block keeps the maps in registers fo
 def area_tile(dtype=torch.float64):
     """Cells of the plane one block of mlx_area_mean reduces for a record of ``dtype`` (a torch or
     numpy float32 / float64): the order of summation is a function of this and of the plane."""
-    name = str(dtype).replace("torch.", "")
-    name = name if name in ("float32", "float64") else np.dtype(dtype).name
-    if name not in ("float32", "float64"):
-        raise TypeError(f"records are float32 or float64, not {name}")
-    return int(_lib.load_area().mlx_area_tile(DTYPE_F64 if name == "float64" else DTYPE_F32))
+    return int(_lib.load_area().mlx_area_tile(_query_dtype(dtype)))
 
 
 def _area_slot(slot, nslots, plane, device):
@@ -1276,6 +1288,13 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
+def layer_record_blocks(nrec):
+    """Block rows along the records of a layer_integral call over ``nrec`` records
+    (mlx_layer_record_blocks): ``min(ceil(nrec / LAYER_STEPS), cap)``; past the cap a block goes on
+    to further groups of records.  0 for nrec <= 0."""
+    return int(_lib.load_layer().mlx_layer_record_blocks(int(nrec)))
+
+
 def layer_groups(nlayers, cap=LAYER_MAX):
     """``[(start, count)]``: the layers in launches of at most ``cap`` (as regional.slot_groups)"""
     return [(s, min(cap, nlayers - s)) for s in range(0, nlayers, cap)]
@@ -1342,6 +1361,12 @@ def filter_window_edges():
         if e <= 0:
             return tuple(edges)
         edges.append(e)
+
+
+def filter_tiles_per_block(nt, n, cells_per_lane):
+    """Consecutive time tiles one block of mlx_filter_apply walks for an (nt, n) record whose lanes
+    hold ``cells_per_lane`` cells (mlx_filter_tiles_per_block); 0 for refused arguments."""
+    return int(_lib.load_filter().mlx_filter_tiles_per_block(int(nt), int(n), int(cells_per_lane)))
 
 
 def filter_weights(w, nt):

@@ -24,6 +24,7 @@
 // grid = (cell tiles, time chunks): a block walks a run of consecutive tiles.  How many chunks
 // there are is a matter of occupancy alone: no output is ever split between threads and there are
 // no atomics, so results depend neither on the launch geometry nor on how a caller blocks the cells.
+// mlx_filter_tiles_per_block reports the length of a block's run.
 //
 // Cells that do not fill a pack (n not a multiple of it, or rows that are then not aligned) are
 // handled by the narrower instantiations, down to one cell per lane.
@@ -207,15 +208,31 @@ struct FilterArgs {
   hipStream_t st;
 };
 
+// the record extents mlx_filter_apply takes
+inline bool filter_shape_ok(int64_t nt, int64_t n) {
+  int64_t total;
+  return !(nt <= 0 || n <= 0 || nt >= kMaxSteps || n > kMaxCells ||
+           __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
+           ceil_div(n, kFilterBlock) > 2147483647LL);
+}
+
+// Consecutive time tiles a block walks (the kernel's `per`) for v cells a lane: the one rule, which
+// mlx_filter_tiles_per_block reports and launch_filter launches by.
+inline int64_t filter_tiles_per_block(int64_t nt, int64_t n, int v) {
+  const int64_t gx = ceil_div(n, (int64_t)kFilterBlock * v);
+  const int64_t ntiles = ceil_div(nt, kFilterSteps);
+  int64_t gy = ceil_div(kFilterTargetBlocks, gx);
+  gy = gy > ntiles ? ntiles : gy;
+  gy = gy > (int64_t)kFilterMaxGridY ? (int64_t)kFilterMaxGridY : gy;
+  return ceil_div(ntiles, gy);
+}
+
 template <typename TIn, typename TOut, int V, bool NORM>
 int launch_filter(const FilterArgs& a) {
   const int64_t gx = ceil_div(a.n, (int64_t)kFilterBlock * V);
   const int64_t ntiles = ceil_div(a.nt, kFilterSteps);
-  int64_t gy = ceil_div(kFilterTargetBlocks, gx);
-  gy = gy > ntiles ? ntiles : gy;
-  gy = gy > (int64_t)kFilterMaxGridY ? (int64_t)kFilterMaxGridY : gy;
-  const int64_t per = ceil_div(ntiles, gy);
-  gy = ceil_div(ntiles, per);
+  const int64_t per = filter_tiles_per_block(a.nt, a.n, V);
+  const int64_t gy = ceil_div(ntiles, per);
   hipLaunchKernelGGL((k_time_filter<TIn, TOut, V, NORM>), dim3((unsigned)gx, (unsigned)gy),
                      dim3(kFilterBlock), 0, a.st, (const TIn*)a.y, a.w, a.W, a.w_stride, a.lead,
                      a.min_count, a.nt, a.n, (int32_t)per, (TOut*)a.out);
@@ -251,6 +268,13 @@ int64_t mlx_filter_window_edge(int i) {
   return 0;
 }
 
+int64_t mlx_filter_tiles_per_block(int64_t nt, int64_t n, int cells_per_lane) {
+  if (!filter_shape_ok(nt, n)) return 0;
+  if (cells_per_lane != 1 && cells_per_lane != 2 && cells_per_lane != 4) return 0;
+  if (n % cells_per_lane != 0) return 0;  // (no launch has lanes that wide)
+  return filter_tiles_per_block(nt, n, cells_per_lane);
+}
+
 int mlx_filter_apply(const void* y, int dtype, const double* w, int64_t W, int64_t w_stride,
                     int64_t lead, int64_t min_count, int flags, int64_t nt, int64_t n, void* out,
                     int out_dtype, void* stream) {
@@ -258,10 +282,7 @@ int mlx_filter_apply(const void* y, int dtype, const double* w, int64_t W, int64
   if (!is_float_dtype(dtype) || !is_float_dtype(out_dtype))
     return fail(MLX_E_ENUM, "dtype and out_dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
   if (flags & ~MLX_FILTER_NORMALISE) return fail(MLX_E_ENUM, "unknown MLX_FILTER_* flag");
-  int64_t total;
-  if (nt <= 0 || n <= 0 || nt >= kMaxSteps || n > kMaxCells ||
-      __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
-      ceil_div(n, kFilterBlock) > 2147483647LL)
+  if (!filter_shape_ok(nt, n))
     return fail(MLX_E_SHAPE, "need 0 < nt < 2^30, 0 < n <= 2^38, nt*n addressable");
   if (W < 1 || W > nt) return fail(MLX_E_SHAPE, "need 1 <= W <= nt");
   if (lead < 0 || lead >= W) return fail(MLX_E_SHAPE, "need 0 <= lead < W");

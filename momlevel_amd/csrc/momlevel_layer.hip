@@ -157,6 +157,13 @@ __global__ __launch_bounds__(kLayerBlock) void k_layer_integral(
   }
 }
 
+// gridDim.y of a call over nrec > 0 records: one block row per kLayerSteps records up to the cap,
+// past which the rows stride.  The one rule: mlx_layer_record_blocks reports it, the launch uses it.
+inline int64_t layer_record_blocks(int64_t nrec) {
+  const int64_t nrb = ceil_div(nrec, kLayerSteps);
+  return nrb < (int64_t)kLayerMaxGridY ? nrb : (int64_t)kLayerMaxGridY;
+}
+
 template <typename TV, int NLC>
 void layer_launch(bool generic, dim3 grid, hipStream_t st, const void* x, int64_t nrec, int64_t nz,
                   int64_t plane, const double* z_i, const double* depth, const LayerBounds& lb,
@@ -187,6 +194,11 @@ void layer_dispatch(bool generic, dim3 grid, hipStream_t st, const void* x, int6
 }  // namespace mlx
 
 extern "C" int mlx_layer_steps(void) { return mlx::kLayerSteps; }
+
+extern "C" int mlx_layer_record_blocks(int64_t nrec) {
+  if (nrec <= 0 || nrec > mlx::kLayerMaxCells) return 0;
+  return (int)mlx::layer_record_blocks(nrec);
+}
 
 extern "C" int mlx_layer_integral(const void* x, int x_dtype, int64_t nrec, int64_t nz,
                                   int64_t plane, const double* z_i, const double* depth,
@@ -227,9 +239,7 @@ extern "C" int mlx_layer_integral(const void* x, int x_dtype, int64_t nrec, int6
   // packs: every level of every record starts on a 16-byte boundary, and so does every out plane
   const bool generic = plane % vec != 0 || !aligned(x, 16) || !aligned(out, 16);
   const int64_t per_block = (int64_t)kLayerBlock * (generic ? 1 : vec);
-  const int64_t nrb = ceil_div(nrec, kLayerSteps);
-  const dim3 grid((unsigned)ceil_div(plane, per_block),
-                  (unsigned)(nrb < (int64_t)kLayerMaxGridY ? nrb : (int64_t)kLayerMaxGridY));
+  const dim3 grid((unsigned)ceil_div(plane, per_block), (unsigned)layer_record_blocks(nrec));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (f64)
     layer_dispatch<double>(generic, grid, st, x, nrec, nz, plane, z_i, depth, lb, nlayers, surface,

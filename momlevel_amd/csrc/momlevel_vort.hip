@@ -372,6 +372,15 @@ inline bool vort_tile_grid(int64_t ny, int64_t nx, int P, int64_t* gy, int64_t* 
   return *gy <= 65535 && *gz <= 65535 && *gy * *gz <= kVortMaxBlocks;
 }
 
+// Records one launch of the packed path takes (the record is the grid's x) for a corner plane of
+// (ny, nx) in packs of P cells, with that record's grid in *gy, *gz; 0 where the plane's shape
+// sends it cell by cell.  The one rule: mlx_vort_records_per_launch reports it, zeta_launch and
+// pv_launch cut their calls by it.
+inline int64_t vort_records_per_launch(int64_t ny, int64_t nx, int P, int64_t* gy, int64_t* gz) {
+  if (nx % P != 0 || !vort_tile_grid(ny, nx, P, gy, gz)) return 0;
+  return kVortMaxBlocks / (*gy * *gz);
+}
+
 template <typename TF, typename TM>
 int zeta_launch(const void* u_, const void* v_, const void* dx_, const void* dy_, const void* area_,
                 int64_t nrec, int64_t ny, int64_t nx, int s, void* out_, hipStream_t st) {
@@ -384,16 +393,17 @@ int zeta_launch(const void* u_, const void* v_, const void* dx_, const void* dy_
   const TM* area = (const TM*)area_;
   TA* out = (TA*)out_;
   int64_t gy, gz;
-  const bool packed = s == 0 && nx % P == 0 && vort_aligned(u, sizeof(TF) * P) &&
+  const int64_t step = vort_records_per_launch(ny, nx, P, &gy, &gz);
+  const bool packed = s == 0 && step > 0 && vort_aligned(u, sizeof(TF) * P) &&
                       vort_aligned(v, sizeof(TF) * P) && vort_aligned(dx, sizeof(TM) * P) &&
                       vort_aligned(dy, sizeof(TM) * P) && vort_aligned(area, sizeof(TM) * P) &&
-                      vort_aligned(out, 16) && vort_tile_grid(ny, nx, P, &gy, &gz);
+                      vort_aligned(out, 16);
   if (!packed) {
     hipLaunchKernelGGL((k_vort_zeta_cells<TF, TM>), dim3(vort_cell_grid(nrec * ny * nx)),
                        dim3(kVortBlock), 0, st, u, v, dx, dy, area, out, nrec, ny, nx, s);
     return detail::hip_status(hipGetLastError(), "k_vort_zeta_cells launch");
   }
-  const int64_t plane = ny * nx, step = kVortMaxBlocks / (gy * gz);  // records a launch
+  const int64_t plane = ny * nx;
   for (int64_t r0 = 0; r0 < nrec; r0 += step) {
     const int64_t nr = nrec - r0 < step ? nrec - r0 : step;
     hipLaunchKernelGGL((k_vort_zeta<TF, TM>), dim3((unsigned)nr, (unsigned)gy, (unsigned)gz),
@@ -415,16 +425,17 @@ int pv_launch(const void* zeta_, const void* f_, const void* n2_, int64_t nrec, 
   TR* out = (TR*)out_;
   const TN g = (TN)gravity;  // (a python float is weak: it takes N^2's dtype)
   int64_t gy, gz;
-  const bool packed = (s == 0 || !interp) && nx % P == 0 && vort_aligned(zeta, sizeof(TZ) * P) &&
+  const int64_t step = vort_records_per_launch(ny, nx, P, &gy, &gz);
+  const bool packed = (s == 0 || !interp) && step > 0 && vort_aligned(zeta, sizeof(TZ) * P) &&
                       vort_aligned(f, sizeof(TC) * P) && vort_aligned(n2, sizeof(TN) * P) &&
-                      vort_aligned(out, 16) && vort_tile_grid(ny, nx, P, &gy, &gz);
+                      vort_aligned(out, 16);
   if (!packed) {
     hipLaunchKernelGGL((k_vort_pv_cells<TZ, TC, TN>), dim3(vort_cell_grid(nrec * ny * nx)),
                        dim3(kVortBlock), 0, st, zeta, f, n2, out, nrec, ny, nx, interp,
                        interp ? s : 0, g, cm);
     return detail::hip_status(hipGetLastError(), "k_vort_pv_cells launch");
   }
-  const int64_t plane = ny * nx, step = kVortMaxBlocks / (gy * gz);
+  const int64_t plane = ny * nx;
   for (int64_t r0 = 0; r0 < nrec; r0 += step) {
     const int64_t nr = nrec - r0 < step ? nrec - r0 : step;
     const dim3 grid((unsigned)nr, (unsigned)gy, (unsigned)gz);
@@ -473,6 +484,14 @@ extern "C" int64_t mlx_vort_tile_width(int arith_dtype) {
   if (arith_dtype == MLX_DTYPE_F64) return (int64_t)mlx::kVortLanes * 2;
   if (arith_dtype == MLX_DTYPE_F32) return (int64_t)mlx::kVortLanes * 4;
   return 0;
+}
+
+extern "C" int64_t mlx_vort_records_per_launch(int64_t ny, int64_t nx, int arith_dtype) {
+  if (ny < 1 || nx < 1 || ny > mlx::kVortMaxCells || nx > mlx::kVortMaxCells / ny ||
+      !mlx::vort_dtype_ok(arith_dtype))
+    return 0;
+  int64_t gy, gz;
+  return mlx::vort_records_per_launch(ny, nx, 16 / (int)mlx::vort_elem(arith_dtype), &gy, &gz);
 }
 
 extern "C" int mlx_vort_rel_vort(const void* u, const void* v, int field_dtype, const void* dx,

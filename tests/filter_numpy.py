@@ -10,6 +10,10 @@ or acc.  float32 records are widened first; a float32 result is ``.astype(float3
 
 With weights of 1 and ``normalise`` this is bit-identical to ``numpy.nanmean(y[lo:hi], axis=0)``
 masked by the valid count (``rolling_mean_nanmean`` below; checked in tests/test_filter_host.py).
+
+``time_filter_taps`` is the same contract for records of 10^5 steps, where the loop over nt x W
+takes tens of seconds: a loop over the W taps alone, each applied to the whole record shifted.  It
+is held to ``time_filter`` bit for bit in tests/test_filter_host.py.
 """
 
 import warnings
@@ -43,6 +47,57 @@ def time_filter(y, w, lead, min_count=None, normalise=False):
             res = acc / wsum if normalise else acc
             out[t] = np.where(cnt < min_count, np.nan, res)
     return out
+
+
+def tap_sums(y, w, lead):
+    """``(acc, wsum, cnt)`` of every output step at once, (nt, ...) each: the loop of ``time_filter``
+    turned inside out.  It runs over the taps k only, ascending; tap k of ALL outputs is the record
+    shifted by k - lead, read from a copy padded with NaN rows for the steps outside [0, nt).  Per
+    output the start values (-0.0, 0, 0), the order of the adds and the ``where(valid, w * y, 0.0)``
+    terms are ``time_filter``'s, so the sums are its sums bit for bit (tests/test_filter_host.py)."""
+    y64 = np.asarray(y).astype(np.float64)
+    nt = y64.shape[0]
+    w = np.asarray(w, dtype=np.float64)
+    W = w.shape[-1]
+    assert 1 <= W <= nt and 0 <= lead < W and (w.ndim == 1 or w.shape == (nt, W))
+    cells = y64.shape[1:]
+    padded = np.full((nt + W - 1,) + cells, np.nan)
+    padded[lead:lead + nt] = y64  # step s sits in row s + lead: tap k of output t is row t + k
+    acc = np.full(y64.shape, -0.0)
+    wsum = np.zeros(y64.shape)
+    cnt = np.zeros(y64.shape, dtype=np.int64)
+    term = np.empty(y64.shape)  # (buffers written in place: the record may be tens of MB)
+    mask = np.empty(y64.shape, dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(W):
+            rows = padded[k:k + nt]
+            wk = w[k] if w.ndim == 1 else w[:, k].reshape((nt,) + (1,) * len(cells))
+            np.isnan(rows, out=mask)  # not valid
+            np.multiply(wk, rows, out=term)
+            np.copyto(term, 0.0, where=mask)  # where(valid, w[k] * y, 0.0)
+            acc += term
+            np.copyto(term, wk)
+            np.copyto(term, 0.0, where=mask)  # where(valid, w[k], 0.0)
+            wsum += term
+            np.logical_not(mask, out=mask)  # valid
+            cnt += mask
+    return acc, wsum, cnt
+
+
+def finish(acc, wsum, cnt, min_count, normalise=False):
+    """the result of the contract from the three sums of ``tap_sums``"""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        res = acc / wsum if normalise else acc
+    return np.where(cnt < min_count, np.nan, res)
+
+
+def time_filter_taps(y, w, lead, min_count=None, normalise=False):
+    """``time_filter`` for long records: the same float64 (nt, ...) result, bit for bit, from a
+    loop over the W taps instead of over nt x W (``tap_sums``)"""
+    W = np.asarray(w).shape[-1]
+    min_count = W if min_count is None else int(min_count)
+    assert 1 <= min_count <= W
+    return finish(*tap_sums(y, w, lead), min_count, normalise)
 
 
 def window_bounds(t, window, center, nt):

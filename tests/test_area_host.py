@@ -64,7 +64,7 @@ def test_other_tables_and_the_abi_version_are_untouched():
         for table in (_lib.SIGNATURES, _lib.TREND_SIGNATURES, _lib.CLIM_SIGNATURES,
                       _lib.GAUGE_SIGNATURES, _lib.SPICE_SIGNATURES, _lib.VORT_SIGNATURES):
             assert name not in table
-    assert len(_lib.SIGNATURES) == 28 and len(_lib.VORT_SIGNATURES) == 4
+    assert len(_lib.SIGNATURES) == 28 and len(_lib.VORT_SIGNATURES) == 5
     assert _lib.ABI_VERSION == 9 and _lib.load().mlx_version() == 9
 
 

@@ -1,4 +1,5 @@
-"""CPU: the numpy restatement tests/filter_numpy.py against numpy's own nanmean and polyfit, the C
+"""CPU: the numpy restatement tests/filter_numpy.py against numpy's own nanmean and polyfit (and its
+tap-loop form for long records against the restatement, bit for bit), the C
 ABI of include/momlevel_filter.h (symbols, binding table, argument errors -- they precede every HIP
 call), the host-side tables of momlevel_amd.filters (window placement, Lanczos weights, the running
 least-squares table) and every Python-level refusal.  No GPU."""
@@ -20,7 +21,8 @@ from momlevel_amd.labeled import DataArray, Dataset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "momlevel_filter.h")
-NAMES = ["mlx_filter_apply", "mlx_filter_tile", "mlx_filter_window_edge"]
+NAMES = ["mlx_filter_apply", "mlx_filter_tile", "mlx_filter_tiles_per_block",
+         "mlx_filter_window_edge"]
 
 
 def _record(nt=60, n=37, seed=3):
@@ -47,6 +49,39 @@ def test_restatement_is_nanmean_over_the_window(window, center):
         assert_bit_equal(got, fn.rolling_mean_nanmean(y, window, center, mp),
                          f"window {window} min_periods {mp}")
     assert np.isnan(got[:, 4]).all()
+
+
+WEIGHT_SEED = 11
+
+
+@pytest.mark.parametrize("window, center", [(1, True), (4, True), (5, True), (12, False), (13, True),
+                                            (60, True)])
+def test_the_tap_loop_is_the_restatement_bit_for_bit(window, center):
+    """filter_numpy.time_filter_taps (a loop over the taps, for long records) against time_filter
+    (the loop over steps and taps): both leads and one that is neither, every min_count that
+    matters, both normalisations, a row and a table of weights"""
+    y = _record()
+    y[:, 7] = -0.0  # (the sign of a zero sum is part of the bits)
+    nt = y.shape[0]
+    rng = np.random.default_rng(WEIGHT_SEED + window)
+    row = rng.normal(0.0, 1.0, window)
+    table = rng.normal(0.0, 1.0, (nt, window))
+    leads = sorted({filters.window_lead(window, center), filters.window_lead(window, not center),
+                    (window - 1) // 3})
+    for lead in leads:
+        for w in (np.ones(window), row, table):
+            sums = fn.tap_sums(y, w, lead)
+            for mc in sorted({1, min(2, window), window}):
+                for norm in (False, True):
+                    want = fn.time_filter(y, w, lead, mc, norm)
+                    what = f"W={window} lead={lead} w{np.shape(w)} mc={mc} norm={norm}"
+                    assert_bit_equal(fn.time_filter_taps(y, w, lead, mc, norm), want, what)
+                    assert_bit_equal(fn.finish(*sums, mc, norm), want, what + " (finish)")
+        assert_bit_equal(fn.time_filter_taps(y, row, lead), fn.time_filter(y, row, lead), "default mc")
+    y32 = y.astype(np.float32)
+    assert_bit_equal(fn.time_filter_taps(y32, row, leads[0], 1), fn.time_filter(y32, row, leads[0], 1),
+                     "a float32 record")
+    assert fn.time_filter_taps(y32, row, leads[0], 1).dtype == np.float64
 
 
 def test_restatement_on_a_hand_computed_series():
@@ -236,13 +271,50 @@ def test_geometry_queries():
     assert lib.mlx_filter_window_edge(len(edges)) == 0 and lib.mlx_filter_window_edge(-1) == 0
 
 
+def test_tiles_per_block_is_plain_arithmetic():
+    """per = ceil(ntiles / gy) with gy = min(ceil(target / gx), ntiles): 1 until the launch has its
+    blocks without cutting time, then it grows with the cells and with the record"""
+    per, tile = core.filter_tiles_per_block, core.filter_tile()
+    assert per(1, 1, 1) == 1 and per(96, 2052, 4) == 1 and per(96, 1023, 1) == 1
+    # one block of cells: every tile has a block of its own until there are more tiles than the
+    # target; the first record past it gives two tiles to all blocks but the last
+    hi = 1
+    while per(tile * hi + 1, 6, 2) == 1:
+        hi *= 2
+    lo = hi // 2  # the most tiles that still get a block each lies in (lo, hi]: bisect
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if per(tile * mid + 1, 6, 2) == 1 else (lo, mid)
+    target = hi
+    assert 1 < target <= 65535
+    assert per(tile * target, 6, 2) == 1 and per(tile * target + 1, 6, 2) == 2
+    assert per(tile * 2 * target, 6, 2) == 2 and per(tile * 2 * target + 1, 6, 2) == 3
+    for v in (1, 2, 4):  # one block of cells at every width
+        assert per(tile * target + 1, 4 * v, v) == 2
+    # per never shrinks along either axis, and the blocks along time cover the tiles
+    for v, n in ((1, 5), (2, 6), (4, 8), (1, 190465), (4, 1 << 21)):
+        last = 1
+        for nt in (1, tile, tile + 1, 96, 1200, tile * target + 1, 1 << 20):
+            p = per(nt, n, v)
+            assert last <= p <= -(-nt // tile), (nt, n, v)
+            last = p
+    wide = [per(96, n, 1) for n in (1, 1 << 10, 1 << 16, 1 << 18, 1 << 20, 1 << 24)]
+    assert wide == sorted(wide) and wide[0] == 1 and wide[-1] == -(-96 // tile)
+    # refused: extents mlx_filter_apply refuses, widths that are no pack or do not divide n
+    lib = _lib.load_filter()
+    for nt, n, v in ((0, 6, 2), (-1, 6, 2), (96, 0, 1), (96, -4, 4), (1 << 30, 6, 2),
+                     (96, (1 << 38) + 1, 1), (1 << 29, 1 << 38, 2), (96, 6, 0), (96, 6, 3),
+                     (96, 6, 8), (96, 6, -1), (96, 6, 4), (96, 5, 2)):
+        assert lib.mlx_filter_tiles_per_block(nt, n, v) == 0, (nt, n, v)
+
+
 def test_other_tables_and_the_abi_version_are_untouched():
     for name in _lib.FILTER_SIGNATURES:
         for table in (_lib.SIGNATURES, _lib.TREND_SIGNATURES, _lib.CLIM_SIGNATURES,
                       _lib.GAUGE_SIGNATURES, _lib.SPICE_SIGNATURES, _lib.VORT_SIGNATURES,
                       _lib.AREA_SIGNATURES, _lib.LAYER_SIGNATURES):
             assert name not in table
-    assert len(_lib.SIGNATURES) == 28 and len(_lib.LAYER_SIGNATURES) == 2
+    assert len(_lib.SIGNATURES) == 28 and len(_lib.LAYER_SIGNATURES) == 3
     assert _lib.ABI_VERSION == 9 and _lib.load().mlx_version() == 9
 
 

@@ -25,6 +25,13 @@ Gates (none taken from what the kernels give):
 Every gated figure is printed before it is asserted.  Worst figures on an MI355X, of the 45 fits
 and the 70 x 8 projections: line 1.78e-15 and intercept 1.21e-15 (nt=7, 1030 cells, float64), slope
 3.57e-12 (nt=257, 1023 cells, float32); projection 3.70e-16 (nt=257, 1026 cells, float64).
+
+Records of 4096 and 4097 steps (513 float64 and 1023 float32 cells) take the fits to windows longer
+than 256 steps: sixteen windows -- asserted through mlx_time_fit_workspace_bytes -- of 256, and of
+257 with a last one of 242, which ends every window in the remainder of the fit loop's unroll of 8.
+Same measures, same gate.  Worst figures on an MI355X, of those 4 fits and 2 x 8 projections: line
+1.05e-15 (nt=4096, 513 cells, float64), intercept 6.36e-16 (nt=4096, 1023 cells, float32), slope
+2.85e-14 (nt=4097, 513 cells, float64); projection 4.53e-17 (nt=4097, 1023 cells, float32).
 """
 
 import numpy as np
@@ -33,7 +40,7 @@ import torch
 
 import trend_numpy as tn
 from conftest import assert_bit_equal
-from momlevel_amd import core, trend
+from momlevel_amd import _lib, core, trend
 
 pytestmark = pytest.mark.gpu
 
@@ -128,6 +135,10 @@ FIT_CASES = ([(257, d, n) for d, n in CELLS]
 @pytest.mark.parametrize("nt, dtype, n", FIT_CASES,
                          ids=[f"{nt}-{np.dtype(d).name}-{n}" for nt, d, n in FIT_CASES])
 def test_linfit_across_blocks_and_windows(nt, dtype, n):
+    _linfit_case(nt, dtype, n)
+
+
+def _linfit_case(nt, dtype, n):
     x = _axis(nt)
     y = _record(nt, n, dtype, seed=nt * 31 + n)
     xt, s, xmean = trend.fit_axis(x)
@@ -158,6 +169,40 @@ def test_linfit_across_blocks_and_windows(nt, dtype, n):
     assert line <= GATE and icpt <= GATE and slope <= GATE
 
 
+# Records long enough for the fit's time windows to outgrow 256 steps (a daily record): from sixteen
+# windows on the window is ceil(nt / 16).  4096: sixteen windows of exactly 256; 4097: sixteen of 257
+# -- no multiple of the fit loop's unroll of 8, so every window ends in the remainder loop -- the
+# last one ragged.  One cell a lane at either dtype, three and four blocks, the last of one cell.
+NT_LONG = (4096, 4097)
+LONG_CELLS = [(np.float64, 513), (np.float32, 1023)]
+LONG_IDS = [f"{np.dtype(d).name}-{n}" for d, n in LONG_CELLS]
+LONG_WINDOWS = 16
+
+
+def _fit_windows(nt, n, nterms):
+    """time windows of a fit over (nt, n), from the workspace the library asks for: ``nterms``
+    float64 partial sums per cell and window"""
+    nbytes = int(_lib.load_trend().mlx_time_fit_workspace_bytes(nt, n, nterms))
+    assert nbytes > 0 and nbytes % (nterms * n * 8) == 0
+    return nbytes // (nterms * n * 8)
+
+
+def _assert_long_windows(nt, n, nterms, what):
+    windows = _fit_windows(nt, n, nterms)
+    shortest = -(-nt // windows)  # no window of `windows` equal ones can be shorter
+    print(f"{what} nt={nt} n={n}: {windows} windows of {shortest} steps, the last of "
+          f"{nt - (windows - 1) * shortest}")
+    assert windows == LONG_WINDOWS
+    assert shortest == (256 if nt == 256 * LONG_WINDOWS else 257)
+
+
+@pytest.mark.parametrize("nt", NT_LONG)
+@pytest.mark.parametrize("dtype, n", LONG_CELLS, ids=LONG_IDS)
+def test_linfit_windows_longer_than_256_steps(dtype, n, nt):
+    _assert_long_windows(nt, n, 5, "linfit")
+    _linfit_case(nt, dtype, n)
+
+
 # ---- time_project -------------------------------------------------------------------------------
 NT_PROJECT = (1, 3, 4, 5, 256, 257, 513)  # the unroll of 4; <= 256: one window, written to coef itself
 
@@ -176,6 +221,18 @@ def _project_reference(P, y):
 @pytest.mark.parametrize("nt", NT_PROJECT)
 @pytest.mark.parametrize("dtype, n", CELLS, ids=CELL_IDS)
 def test_project_every_k_across_blocks_and_windows(dtype, n, nt):
+    _project_case(dtype, n, nt)
+
+
+@pytest.mark.parametrize("dtype, n", LONG_CELLS, ids=LONG_IDS)
+def test_project_windows_longer_than_256_steps(dtype, n):
+    nt = NT_LONG[-1]
+    for K in (1, 8):
+        _assert_long_windows(nt, n, K, f"project K={K}")
+    _project_case(dtype, n, nt)
+
+
+def _project_case(dtype, n, nt):
     v = _pack(dtype, n)
     seam = 256 * v if 256 * v + 1 < n else 255 * v  # the first (or last) pack of a block
     y = _record(nt, n, dtype, seed=nt * 17 + n, gaps=False)

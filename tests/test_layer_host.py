@@ -17,7 +17,7 @@ from momlevel_amd.labeled import DataArray, Dataset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "momlevel_layer.h")
-NAMES = ["mlx_layer_integral", "mlx_layer_steps"]
+NAMES = ["mlx_layer_integral", "mlx_layer_record_blocks", "mlx_layer_steps"]
 INF = np.inf
 
 
@@ -165,11 +165,24 @@ def test_layer_header_declares_exactly_the_two_symbols():
             assert argtypes == []
             continue
         assert argtypes == [next(v for k, v in ctype.items() if a.startswith(k)) for a in args], name
-        assert args[-1] == "void *stream", name  # the caller's stream last
+        if name != "mlx_layer_record_blocks":  # (a query: host arithmetic, no stream)
+            assert args[-1] == "void *stream", name  # the caller's stream last
     assert re.findall(r"#define MLX_(LAYER_[A-Z_]+)\s+(\d+)", text) == [("LAYER_MAX", "8")]
     assert _lib.LAYER_MAX == core.LAYER_MAX == 8
     assert core.LAYER_STEPS == lib.mlx_layer_steps() >= 1
     assert _lib.load_layer() is _lib.load()
+
+
+def test_record_blocks_is_plain_arithmetic():
+    """min(ceil(nrec / steps), cap): a block row per group of records up to the cap"""
+    S, blocks = core.LAYER_STEPS, core.layer_record_blocks
+    cap = blocks(10 ** 9)
+    assert 1 < cap <= 65535 and blocks(1 << 38) == cap  # (a grid's y holds at most 65535)
+    for nrec in (1, S - 1, S, S + 1, 2 * S + 3, 1000, S * (cap - 1), S * (cap - 1) + 1):
+        if nrec >= 1:
+            assert blocks(nrec) == -(-nrec // S), nrec
+    assert blocks(S * cap) == cap == blocks(S * cap + 1) == blocks(S * cap + S + 1)
+    assert blocks(0) == 0 and blocks(-5) == 0 and blocks((1 << 38) + 1) == 0
 
 
 def test_other_tables_and_the_abi_version_are_untouched():

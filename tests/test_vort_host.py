@@ -125,7 +125,8 @@ def test_vort_header_binding_and_exports_agree():
     text = _header_text()
     declared = sorted(set(re.findall(r"\b(mlx_[a-z0-9_]+)\s*\(", text)))
     assert declared == sorted(_lib.VORT_SIGNATURES) == [
-        "mlx_vort_pv", "mlx_vort_rel_vort", "mlx_vort_rossby", "mlx_vort_tile_width"]
+        "mlx_vort_pv", "mlx_vort_records_per_launch", "mlx_vort_rel_vort", "mlx_vort_rossby",
+        "mlx_vort_tile_width"]
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in momlevel_vort.h but not exported"
@@ -151,6 +152,31 @@ def test_vort_header_binding_and_exports_agree():
     assert core.vort_tile() == (_lib.VORT_TILE_LANES * 2, _lib.VORT_TILE_LANES * 4, _lib.VORT_TILE_H,
                                 _lib.VORT_TILE_BANDS)
     assert lib.mlx_vort_tile_width(7) == 0
+
+
+def test_records_per_launch_is_plain_arithmetic():
+    """step = budget // (tiles of one record): the budget is what one tile a record gives, a plane
+    of t tiles gets a t-th of it, and a plane that cannot be moved in packs gets 0"""
+    step = core.vort_records_per_launch
+    W64, W32, H, bands = core.vort_tile()
+    rows = H * bands  # rows of a block
+    for dt, W, P in ((np.float64, W64, 2), (np.float32, W32, 4)):
+        budget = step(1, P, dt)
+        assert budget > 1 and step(2, P, dt) == step(rows, W, dt) == budget  # one tile a record
+        for ny, nx, tiles in ((rows + 1, P, 2), (rows, W + P, 2), (rows + 1, W + P, 4),
+                              (3 * rows, 2 * W, 6), (1080, 1440 - 1440 % P,
+                                                     -(-1080 // rows) * -(-(1440 - 1440 % P) // W))):
+            assert step(ny, nx, dt) == budget // tiles, (ny, nx, dt)
+        for nx in (1, P - 1, P + 1, W + 1):  # not a whole number of packs: cell by cell
+            assert step(2, nx, dt) == 0
+        assert step(0, P, dt) == 0 and step(2, 0, dt) == 0 and step(-1, P, dt) == 0
+        assert step(1 << 20, P << 20, dt) == 0  # ny * nx > 2^38
+        assert step(rows * 65536, P, dt) == 0 and step(rows * 65535, P, dt) == budget // 65535
+    assert step(2, 2, np.float32) == 0 and step(2, 4, np.float64) == step(2, 2, np.float64)
+    lib = _lib.load_vort()
+    assert lib.mlx_vort_records_per_launch(2, 4, 7) == 0
+    with pytest.raises(TypeError):
+        step(2, 4, np.float16)
 
 
 def test_other_tables_and_the_abi_version_are_untouched():
