@@ -50,6 +50,10 @@ AREA_WINDOW = 32
 LAYER_MAX = 8
 # ---- constants mirrored from include/momlevel_filter.h -----------------------------
 FILTER_NORMALISE = 1
+# ---- constants mirrored from include/momlevel_path.h -------------------------------
+PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
+PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
+PATH_ALIGNED_ALL = 15
 
 
 def flag_tchunk(steps):
@@ -217,6 +221,17 @@ FILTER_SIGNATURES = {
 }
 
 
+# The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
+# load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
+# csrc/momlevel_promote.hip, beside the launchers that go by them.)
+PATH_SIGNATURES = {
+    "mlx_path_eos_map": (_int, [_int, _int, _int, _int, _i64, _i64, _i64, _int, _int,
+                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "mlx_path_eos_promote": (_int, [_int, _int, _int, _int, _int, _int,
+                                    ctypes.POINTER(ctypes.c_int)]),
+}
+
+
 class MomlevelHipError(RuntimeError):
     """Raised when the HIP library is missing or one of its calls fails."""
 
@@ -281,12 +296,13 @@ _GROUPS = {
     "area": (AREA_SIGNATURES, "the area-mean kernels"),
     "layer": (LAYER_SIGNATURES, "the layer-integral kernel"),
     "filter": (FILTER_SIGNATURES, "the time-filter kernel"),
+    "path": (PATH_SIGNATURES, "the path queries of the EOS maps"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
-_layer_bound = _filter_bound = False
+_layer_bound = _filter_bound = _path_bound = False
 
 
 def _load_group(group):
@@ -330,6 +346,10 @@ def load_layer():
 
 def load_filter():
     return _load_group("filter")
+
+
+def load_path():
+    return _load_group("path")
 
 
 def last_error():

@@ -243,55 +243,137 @@ def _pressure(p, nt, nz, ny, nx, device, allow4d):
     raise ValueError(f"pressure of shape {shape} does not broadcast to {(nz, ny, nx)}")
 
 
-def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=None):
-    """K0: pointwise EOS function over a (nt,nz,ny,nx) or (nz,ny,nx) grid -> float64.
-    ``arith``: "exact" | "fused" | None = arith_default("k0", dtype) = exact; applies to the Wright
-    density only."""
-    require_device()
+K0_PATHS = {_lib.PATH_GENERIC: "generic", _lib.PATH_FAST: "fast", _lib.PATH_FAST_P3D: "fast_p3d"}
+PROMOTE_KINDS = {"d": _lib.KIND_F64, "f": _lib.KIND_F32, "w": _lib.KIND_WEAK}
+_PROMOTE_FUNCS = {"inverse_barometer": _lib.FUNC_IBH, "density_ref": _lib.FUNC_DENSITY_REF}
+
+
+def k0_path(dtype, p_mode, eos, func, plane, sT, sS, flags=0, aligned16=_lib.PATH_ALIGNED_ALL):
+    """mlx_path_eos_map: the kernel shape mlx_eos_map (``func`` FUNC_IBH: mlx_inverse_barometer)
+    takes for these arguments, all of them the C ABI's codes; ``aligned16`` the PATH_ALIGNED_* bits
+    of the operands that are 16-byte aligned.  Returns ("generic" | "fast" | "fast_p3d", the cells
+    of a z level one block covers, the time steps one launch takes).  Host arithmetic: no device
+    is needed; arguments mlx_eos_map refuses raise ``MomlevelHipError``."""
+    import ctypes
+
+    cells, steps = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = _lib.load_path().mlx_path_eos_map(int(dtype), int(p_mode), int(eos), int(func), int(plane),
+                                           int(sT), int(sS), int(flags), int(aligned16),
+                                           ctypes.byref(cells), ctypes.byref(steps))
+    if rc < 0:
+        _lib.check(rc, "mlx_path_eos_map")
+    return K0_PATHS[rc], int(cells.value), int(steps.value)
+
+
+def promote_path(kinds, eos="wright", func="density", aligned16=_lib.PATH_ALIGNED_ALL):
+    """mlx_path_eos_promote: (the cells a lane takes -- 4, 2 or 1 --, the result dtype) of
+    mlx_eos_map_promote for operands of ``kinds``, three letters for T, S and p: d = float64 array,
+    f = float32 array, w = python float.  ``aligned16``: the PATH_ALIGNED_* bits of the result and
+    of the operands that are 16-byte aligned (a one-element array counts as aligned; the bits of
+    python floats and of a pressure the function does not read are ignored).  Host arithmetic: no
+    device is needed."""
+    import ctypes
+
+    kind = ctypes.c_int(-1)
+    fid = _PROMOTE_FUNCS.get(func)
+    if fid is None:
+        fid = FUNC_IDS[func]
+    rc = _lib.load_path().mlx_path_eos_promote(*(PROMOTE_KINDS[k] for k in kinds),
+                                               EOS_IDS[eos.lower()], fid, int(aligned16),
+                                               ctypes.byref(kind))
+    if rc < 0:
+        _lib.check(rc, "mlx_path_eos_promote")
+    return rc, (torch.float32 if kind.value == _lib.KIND_F32 else torch.float64)
+
+
+def _is16(t):
+    return t is not None and t.data_ptr() % 16 == 0
+
+
+def _k0_call(T, S, p, eos, f32_mode, flags_of, out):
+    """The arguments of one mlx_eos_map / mlx_inverse_barometer call, shared by the launch and by
+    eos_map_path: (T, S, dt, pt, p_mode, eos id, nt, nz, plane, sT, sS, flags, out, squeeze)."""
     T, S, nt, nz, ny, nx, sT, sS, dt, squeeze = _pair(T, S, f32_mode)
     pt, p_mode = _pressure(p, nt, nz, ny, nx, T.device, allow4d=True)
+    if dt in (DTYPE_T32_S64, DTYPE_T64_S32):
+        return T, S, dt, pt, p_mode, EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, 0, out, squeeze
+    if out is not None and squeeze and out.dim() == 3:
+        out = out.unsqueeze(0)
+    out = _out_like(out, (nt, nz, ny, nx), torch.float64, T.device, "float64")
+    return (T, S, dt, pt, p_mode, EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, flags_of(dt), out,
+            squeeze)
+
+
+def _k0_flags(eos, func, arith):
+    if func == "density" and eos.lower() == "wright":
+        return lambda dt: _arith_flag(arith, "k0", dt)
+    return lambda dt: 0
+
+
+def eos_map_path(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=None, out=None):
+    """The kernel shape ``eos_map`` -- ``func="inverse_barometer"``: ``inverse_barometer`` -- takes
+    for these very operands (mlx_path_eos_map on the arguments the call itself would pass): ("generic"
+    | "fast" | "fast_p3d", cells of a z level per block, time steps per launch).  Nothing is
+    launched.  thetao / so of different dtypes go to eos_map_promote: see promote_path."""
+    require_device()
+    ibh = func == "inverse_barometer"
+    fid = _lib.FUNC_IBH if ibh else FUNC_IDS[func]
+    T, S, dt, pt, p_mode, eid, nt, nz, plane, sT, sS, flags, out, _ = _k0_call(
+        T, S, p, eos, f32_mode, _k0_flags(eos, func, None if ibh else arith), out)
+    if dt in (DTYPE_T32_S64, DTYPE_T64_S32):
+        raise ValueError("thetao / so of different dtypes run on eos_map_promote (promote_path)")
+    bits = ((_lib.PATH_ALIGNED_T if _is16(T) else 0) | (_lib.PATH_ALIGNED_S if _is16(S) else 0)
+            | (_lib.PATH_ALIGNED_OUT if _is16(out) else 0) | (_lib.PATH_ALIGNED_P if _is16(pt) else 0))
+    return k0_path(dt, p_mode, eid, fid, plane, sT, sS, flags, bits)
+
+
+def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=None, out=None):
+    """K0: pointwise EOS function over a (nt,nz,ny,nx) or (nz,ny,nx) grid -> float64.
+    ``arith``: "exact" | "fused" | None = arith_default("k0", dtype) = exact; applies to the Wright
+    density only.  ``out``: a contiguous float64 device tensor of the result's shape to write into
+    (not for thetao / so of different dtypes)."""
+    require_device()
+    T, S, dt, pt, p_mode, eid, nt, nz, plane, sT, sS, flags, out, squeeze = _k0_call(
+        T, S, p, eos, f32_mode, _k0_flags(eos, func, arith), out)
     if dt in (DTYPE_T32_S64, DTYPE_T64_S32):
         # thetao and so of different dtypes: numpy's promotion per sub-expression is the promote
         # kernel's job (one cell per thread over the broadcast operands); exact arithmetic only --
         # an explicit arith="fused" is an error here as it is in K1 / K2
+        if out is not None:
+            raise ValueError("out= is not available for thetao / so of different dtypes")
         _arith_flag(arith, "k0", dt)
-        full = (nt, nz, ny, nx)
+        full = (nt, nz) + tuple(T.shape[-2:])
+        ny, nx = full[2:]
         ops = [(x if x.dim() == 4 else x.unsqueeze(0)).expand(full).reshape(-1) for x in (T, S)]
         if pt is not None and pt.numel() > 1:
             pt = {P_ZPROF: lambda q: q.reshape(1, nz, 1, 1), P_FULL3D: lambda q: q.reshape(1, nz, ny, nx),
                   P_FULL4D: lambda q: q}[p_mode](pt).expand(full).reshape(-1)
-        out = eos_map_promote(ops[0], ops[1], pt, eos=eos, func=func).reshape(full)
-        return out[0] if squeeze else out
-    flags = (_arith_flag(arith, "k0", dt)
-             if (func == "density" and eos.lower() == "wright") else 0)
-    out = torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=T.device)
+        res = eos_map_promote(ops[0], ops[1], pt, eos=eos, func=func).reshape(full)
+        return res[0] if squeeze else res
     _call(_lib.load(), "mlx_eos_map", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), p_mode,
-          EOS_IDS[eos.lower()], FUNC_IDS[func], nt, nz, ny * nx, sT, sS, flags, _ptr(out))
+          eid, FUNC_IDS[func], nt, nz, plane, sT, sS, flags, _ptr(out))
     return out[0] if squeeze else out
 
 
-def inverse_barometer(T, S, p, gravity=9.8, eos="wright", f32_mode="faithful"):
-    """pso * (-1 / (rho(T,S,pso) * gravity)) on a (nt,nz,ny,nx)/(nz,ny,nx) grid -> float64."""
+def inverse_barometer(T, S, p, gravity=9.8, eos="wright", f32_mode="faithful", out=None):
+    """pso * (-1 / (rho(T,S,pso) * gravity)) on a (nt,nz,ny,nx)/(nz,ny,nx) grid -> float64.
+    ``out``: a contiguous float64 device tensor of the result's shape to write into."""
     require_device()
-    T, S, nt, nz, ny, nx, sT, sS, dt, squeeze = _pair(T, S, f32_mode)
-    pt, p_mode = _pressure(p, nt, nz, ny, nx, T.device, allow4d=True)
-    out = torch.empty((nt, nz, ny, nx), dtype=torch.float64, device=T.device)
+    T, S, dt, pt, p_mode, eid, nt, nz, plane, sT, sS, _, out, squeeze = _k0_call(
+        T, S, p, eos, f32_mode, lambda dt: 0, out)
+    if out is None:  # (thetao / so of different dtypes: refused by the library below, as before)
+        out = torch.empty((nt, nz) + tuple(T.shape[-2:]), dtype=torch.float64, device=T.device)
     _call(_lib.load(), "mlx_inverse_barometer", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), p_mode,
-          EOS_IDS[eos.lower()], float(gravity), nt, nz, ny * nx, sT, sS, _ptr(out))
+          eid, float(gravity), nt, nz, plane, sT, sS, _ptr(out))
     return out[0] if squeeze else out
 
 
-def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8):
-    """K0 under numpy's type promotion (mlx_eos_map_promote; csrc/eos_promote.hpp) for the dtype
-    combinations mlx_eos_map does not cover.  Each operand is a python float / int (a WEAK scalar:
-    it takes the dtype of the arrays it meets) or a float32 / float64 device tensor of n elements or
-    of ONE element (used for every cell); ``p`` may be None for the linear EOS.  ``func`` may also
-    be "inverse_barometer" (``gravity`` a python float) or, for the linear EOS, "density_ref" (``p``
-    then carries the constant term RHO_T0_S0 - rho_ref of eos/linear.py:55).  Returns a device tensor of n elements in
-    numpy's result dtype (float32 when no float64 array takes part) holding numpy's values."""
+def _promote_call(T, S, p, eos, func):
+    """The operands of one mlx_eos_map_promote call, shared by the launch and by
+    eos_map_promote_path: (device, n, keep-alive list, the nine operand arguments, func id, kinds,
+    the PATH_ALIGNED_* bits of the operands)."""
     import ctypes
 
-    require_device()
     if p is None and (eos.lower() != "linear" or func in ("inverse_barometer", "density_ref")):
         raise TypeError("p must not be None (only the linear EOS ignores the pressure)")
     tensors = [x for x in (T, S, p) if isinstance(x, torch.Tensor)]
@@ -299,12 +381,14 @@ def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8):
         raise TypeError("at least one operand must be a device tensor")
     device = tensors[0].device
     n = max(int(x.numel()) for x in tensors)
-    keep, args = [], []
+    keep, args, kinds, aligned = [], [], "", 0
+    bit = {"T": _lib.PATH_ALIGNED_T, "S": _lib.PATH_ALIGNED_S, "p": _lib.PATH_ALIGNED_P}
     for name, x in (("T", T), ("S", S), ("p", p)):
         if x is None:
             if name != "p":
                 raise TypeError(f"{name} must not be None")
             args += [None, _lib.KIND_WEAK, 0]
+            kinds += "w"
         elif isinstance(x, torch.Tensor):
             if not x.is_cuda or x.device != device:
                 raise ValueError("operands of one call must live on one GPU")
@@ -314,22 +398,58 @@ def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8):
                 raise ValueError(f"{name} has {x.numel()} elements, expected 1 or {n}")
             x = x.contiguous()
             keep.append(x)
+            stride = 1 if x.numel() == n and n > 1 else 0
             args += [x.data_ptr(), _lib.KIND_F32 if x.dtype == torch.float32 else _lib.KIND_F64,
-                     1 if x.numel() == n and n > 1 else 0]
+                     stride]
+            kinds += "f" if x.dtype == torch.float32 else "d"
+            if stride == 0 or _is16(x):
+                aligned |= bit[name]
         else:
             w = ctypes.c_double(float(x))
             keep.append(w)
             args += [ctypes.addressof(w), _lib.KIND_WEAK, 0]
-    fid = {"inverse_barometer": _lib.FUNC_IBH, "density_ref": _lib.FUNC_DENSITY_REF}.get(func)
+            kinds += "w"
+    fid = _PROMOTE_FUNCS.get(func)
     if fid is None:
         fid = FUNC_IDS[func]
-    out = torch.empty(n, dtype=torch.float64, device=device)
+    return device, n, keep, args, fid, kinds, aligned
+
+
+def eos_map_promote_path(T, S, p, eos="wright", func="density", out=None):
+    """(cells a lane takes, result dtype) of ``eos_map_promote`` for these very operands
+    (mlx_path_eos_promote on the kinds and the alignment the call itself would pass).  Nothing is
+    launched."""
+    require_device()
+    _, _, _, _, _, kinds, aligned = _promote_call(T, S, p, eos, func)
+    return promote_path(kinds, eos, func,
+                        aligned | (_lib.PATH_ALIGNED_OUT if out is None or _is16(out) else 0))
+
+
+def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8, out=None):
+    """K0 under numpy's type promotion (mlx_eos_map_promote; csrc/eos_promote.hpp) for the dtype
+    combinations mlx_eos_map does not cover.  Each operand is a python float / int (a WEAK scalar:
+    it takes the dtype of the arrays it meets) or a float32 / float64 device tensor of n elements or
+    of ONE element (used for every cell); ``p`` may be None for the linear EOS.  ``func`` may also
+    be "inverse_barometer" (``gravity`` a python float) or, for the linear EOS, "density_ref" (``p``
+    then carries the constant term RHO_T0_S0 - rho_ref of eos/linear.py:55).  Returns a device tensor of n elements in
+    numpy's result dtype (float32 when no float64 array takes part) holding numpy's values.
+    ``out``: a contiguous 8-byte aligned device tensor of n elements of that dtype (promote_path
+    tells it) to write into."""
+    import ctypes
+
+    require_device()
+    device, n, keep, args, fid, kinds, _ = _promote_call(T, S, p, eos, func)
+    if out is not None:
+        out = _out_like(out, (n,), promote_path(kinds, eos, func)[1], device)
+    buf = torch.empty(n, dtype=torch.float64, device=device) if out is None else out
     kind = ctypes.c_int(-1)
     _call(_lib.load(), "mlx_eos_map_promote", device, *args, EOS_IDS[eos.lower()], fid,
-          float(gravity), n, _ptr(out), ctypes.byref(kind))
+          float(gravity), n, _ptr(buf), ctypes.byref(kind))
+    if out is not None:
+        return out
     if kind.value == _lib.KIND_F32:  # the kernel stored n float32 values at the start of the buffer
-        return out.view(torch.float32)[:n]
-    return out
+        return buf.view(torch.float32)[:n]
+    return buf
 
 
 def gradient_coefficients(z):

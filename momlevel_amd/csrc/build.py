@@ -67,6 +67,7 @@ TIMED_SOURCES = [
     os.path.join(HERE, "momlevel_promote.hip"),
     os.path.join(HERE, "eos_promote.hpp"),
     os.path.join(ROOT, "include", "momlevel_hip.h"),
+    os.path.join(ROOT, "include", "momlevel_path.h"),
 ]
 # what the library is rebuilt for: every source and header above, and this file
 DEPENDS = sorted({*SOURCES, *TIMED_SOURCES, *(p for f in FEATURES for p in _feature_files(f)),

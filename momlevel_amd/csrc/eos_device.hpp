@@ -637,6 +637,14 @@ __device__ __forceinline__ double eos_eval(int eos, int func, TIn T, TIn S, doub
                             : wright_density_mixed<MODE>((double)T, (double)S, p);
   } else {
   if (func == kIbh) {  // pso * (-1.0 / (rho_conv * gravity))
+    if constexpr (MODE == kF32Faithful) {
+      // the linear density of float32 fields is float32, and numpy keeps it so through the weak
+      // python floats: rho_conv * gravity and -1.0 / (...) round to float32, pso then widens them
+      if (eos == kLinear) {
+        const float rho = 1000.0f + ((-0.2f * T) + (0.8f * S));
+        return p * (double)(-1.0f / (rho * (float)aux));
+      }
+    }
     const double rho = (eos == kLinear) ? linear_density<MODE, TIn>(T, S)
                                         : wright_density<MODE, TIn>(T, S, p);
     return p * (-1.0 / (rho * aux));

@@ -10,6 +10,14 @@ __attribute__((visibility("hidden"))) int fail(int code, const char* msg);
 __attribute__((visibility("hidden"))) int hip_status(hipError_t e, const char* what);
 }  // namespace detail
 
+// The codes of include/momlevel_path.h for the translation units that answer its queries.
+// momlevel_promote.hip includes that header and holds these to it; momlevel_hip.hip is also
+// compiled on its own beside include/momlevel_hip.h alone (tests/test_isa_flags.py).
+namespace path {
+constexpr int kGeneric = 0, kFast = 1, kFastP3D = 2;
+constexpr int kAlignedT = 1, kAlignedS = 2, kAlignedOut = 4, kAlignedP = 8, kAlignedAll = 15;
+}  // namespace path
+
 // calc_dz's arithmetic for one cell and level (derived.py:295-318, fraction=False): the thickness
 // of the part of the level [ztop, zbot] that lies below `top` and above `d`, where d is the sea
 // floor after fillna(0.0) and, with a bottom, np.minimum(depth, bottom).  The ONE definition for

@@ -1325,15 +1325,50 @@ inline int vec_of(int dtype) { return (dtype == MLX_DTYPE_F64 || mixed_dtype(dty
 // (p_mode MLX_P_FULL3D -- `patm` as a (yh,xh) DataArray -- qualifies too where the caller passes
 // the pressure pointer as `p3d`: the fast kernels then read the pressure FIELD with the same
 // 16-byte loads, template argument P3D; a z profile needs no alignment beyond its elements')
-bool fast_layout(int dtype, int p_mode, int eos, int64_t plane, int64_t sT, int64_t sS,
-                 std::initializer_list<const void*> ptrs, const void* p3d = nullptr) {
+// (the rule on what the pointers ARE rather than on the pointers: `ptrs16` every field and result
+// 16-byte aligned, `p3d16` a pressure field was offered for 16-byte loads and is aligned for them;
+// mlx_path_eos_map answers from it without any pointer)
+bool fast_shape(int dtype, int p_mode, int eos, int64_t plane, int64_t sT, int64_t sS, bool ptrs16,
+                bool p3d16) {
   const int vec = vec_of(dtype);
   if (eos != MLX_EOS_WRIGHT) return false;
-  if (p_mode != MLX_P_ZPROF && !(p3d && p_mode == MLX_P_FULL3D && aligned(p3d, 16))) return false;
+  if (p_mode != MLX_P_ZPROF && !(p3d16 && p_mode == MLX_P_FULL3D)) return false;
   if (plane % vec || sT % vec || sS % vec) return false;
+  return ptrs16;
+}
+
+bool fast_layout(int dtype, int p_mode, int eos, int64_t plane, int64_t sT, int64_t sS,
+                 std::initializer_list<const void*> ptrs, const void* p3d = nullptr) {
+  bool ptrs16 = true;
   for (const void* q : ptrs)
-    if (q && !aligned(q, 16)) return false;
-  return true;
+    if (q && !aligned(q, 16)) ptrs16 = false;
+  return fast_shape(dtype, p_mode, eos, plane, sT, sS, ptrs16, p3d && aligned(p3d, 16));
+}
+
+// ---- K0 dispatch --------------------------------------------------------------------------
+// The one rule of mlx_eos_map / mlx_inverse_barometer: eos_map_impl launches by it and
+// mlx_path_eos_map (include/momlevel_path.h) reports it.  The fast kernels take the function at
+// compile time: five of them on float64 fields, the density alone on float32 ones, the density
+// also with a (z,y,x) pressure field (P3D); the inverse barometer has the generic kernel only.
+constexpr int kK0PacksFast = 2;    // fast: 16-byte packs per thread
+constexpr int kK0CellsGeneric = 4;  // generic: scalar cells per thread
+constexpr int64_t kK0LaunchSteps = 32768;  // grid.z carries the time axis (<= 65535)
+
+struct K0Path {
+  int kind;               // path::k* (MLX_PATH_*)
+  int64_t cells_per_block;  // cells of one z level per block
+};
+
+// `aligned16`: path::kAligned* (MLX_PATH_ALIGNED_*) bits of T, S, out and p
+K0Path k0_path(int dtype, int p_mode, int eos, int func, int64_t plane, int64_t sT, int64_t sS,
+               int aligned16) {
+  const int fields = path::kAlignedT | path::kAlignedS | path::kAlignedOut;
+  const bool fast = fast_shape(dtype, p_mode, eos, plane, sT, sS, (aligned16 & fields) == fields,
+                               func == MLX_FUNC_DENSITY && (aligned16 & path::kAlignedP)) &&
+                    (dtype == MLX_DTYPE_F64 || func == MLX_FUNC_DENSITY) && func != MLX_FUNC_IBH;
+  if (!fast) return K0Path{path::kGeneric, (int64_t)kBlock * kK0CellsGeneric};
+  return K0Path{p_mode == MLX_P_FULL3D ? path::kFastP3D : path::kFast,
+                (int64_t)kBlock * vec_of(dtype) * kK0PacksFast};
 }
 
 // The run-time dtype as the compile-time pair of every kernel here: f(TIn{}, MODE constant), TIn the
@@ -1749,21 +1784,31 @@ static int eos_map_impl(const void* T, const void* S, int dtype, const double* p
   if (fma && func != MLX_FUNC_DENSITY)
     return fail(MLX_E_ENUM, "MLX_FLAG_FMA applies to the density only");
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = fast_layout(dtype, p_mode, eos, plane, sT, sS, {T, S, out},
-                                func == MLX_FUNC_DENSITY ? p : nullptr) &&
-                    (dtype == MLX_DTYPE_F64 || func == MLX_FUNC_DENSITY) && func != MLX_FUNC_IBH;
-  const bool p3d = fast && p_mode == MLX_P_FULL3D;
+  const K0Path route = k0_path(dtype, p_mode, eos, func, plane, sT, sS,
+                              (aligned(T, 16) ? path::kAlignedT : 0) |
+                                  (aligned(S, 16) ? path::kAlignedS : 0) |
+                                  (aligned(out, 16) ? path::kAlignedOut : 0) |
+                                  (p && aligned(p, 16) ? path::kAlignedP : 0));
+  const bool fast = route.kind != path::kGeneric;
+  const bool p3d = route.kind == path::kFastP3D;
   const double* pp = p ? p : out;  // never dereferenced for the linear EOS
-  for (int64_t tb = 0; tb < nt; tb += 32768) {
-    const int64_t ntc = (nt - tb < 32768) ? (nt - tb) : 32768;
+  int tile_rc = 0;
+  for (int64_t tb = 0; tb < nt && !tile_rc; tb += kK0LaunchSteps) {
+    const int64_t ntc = (nt - tb < kK0LaunchSteps) ? (nt - tb) : kK0LaunchSteps;
     with_dtype(dtype, [&](auto tin, auto mode) {
       using TIn = decltype(tin);
       constexpr int MODE = decltype(mode)::value;
       // (theta / S of different dtypes were refused above: the maps have no such kernels)
       if constexpr (!IsMixed<MODE>::value) {
-        constexpr int VEC = 16 / sizeof(TIn), UF = 2, UG = 4;  // packs (fast) / cells (generic) per thread
+        // packs (fast) / cells (generic) per thread
+        constexpr int VEC = 16 / sizeof(TIn), UF = kK0PacksFast, UG = kK0CellsGeneric;
         auto launch = [&](auto kernel, int cells) {
-          dim3 grid((unsigned)ceil_div(plane, (int64_t)kBlock * cells), (unsigned)nz, (unsigned)ntc);
+          // the kernel's tile is the path's: the grid is cut by the figure the query reports
+          if ((int64_t)kBlock * cells != route.cells_per_block) {
+            tile_rc = fail(MLX_E_SHAPE, "mlx_eos_map: kernel tile differs from the reported path");
+            return;
+          }
+          dim3 grid((unsigned)ceil_div(plane, route.cells_per_block), (unsigned)nz, (unsigned)ntc);
           hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, st, (const TIn*)T, (const TIn*)S, pp,
                              p_mode, eos, func, nz, plane, sT, sS, tb, aux, out);
         };
@@ -1794,7 +1839,29 @@ static int eos_map_impl(const void* T, const void* S, int dtype, const double* p
       }
     });
   }
+  if (tile_rc) return tile_rc;
   return hip_status(hipGetLastError(), "mlx_eos_map launch");
+}
+
+// include/momlevel_path.h: the rule above, without a launch
+int mlx_path_eos_map(int dtype, int p_mode, int eos, int func, int64_t plane, int64_t sT,
+                     int64_t sS, int flags, int aligned16, int64_t* cells_per_block,
+                     int64_t* launch_steps) {
+  if (flags & ~MLX_FLAG_FMA) return fail(MLX_E_ENUM, "mlx_eos_map takes MLX_FLAG_FMA only");
+  if (int rc = check_dtype(dtype, false)) return rc;
+  if (eos != MLX_EOS_WRIGHT && eos != MLX_EOS_LINEAR) return fail(MLX_E_ENUM, "unknown eos");
+  if (p_mode < MLX_P_SCALAR || p_mode > MLX_P_FULL4D) return fail(MLX_E_ENUM, "unknown p_mode");
+  if (func < MLX_FUNC_DENSITY || func > MLX_FUNC_IBH) return fail(MLX_E_ENUM, "unknown func");
+  if ((flags & MLX_FLAG_FMA) && func != MLX_FUNC_DENSITY)
+    return fail(MLX_E_ENUM, "MLX_FLAG_FMA applies to the density only");
+  if (aligned16 & ~path::kAlignedAll) return fail(MLX_E_ENUM, "unknown bits in aligned16");
+  if (plane <= 0) return fail(MLX_E_SHAPE, "plane must be > 0");
+  if (plane > (int64_t)1 << 40) return fail(MLX_E_SHAPE, "plane too large");
+  if (sT < 0 || sS < 0) return fail(MLX_E_SHAPE, "time strides must be >= 0");
+  const K0Path route = k0_path(dtype, p_mode, eos, func, plane, sT, sS, aligned16);
+  if (cells_per_block) *cells_per_block = route.cells_per_block;
+  if (launch_steps) *launch_steps = kK0LaunchSteps;
+  return route.kind;
 }
 
 int mlx_eos_map(const void* T, const void* S, int dtype, const double* p, int p_mode, int eos,

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "../../include/momlevel_hip.h"
+#include "../../include/momlevel_path.h"
 #include "eos_promote.hpp"
 #include "mlx_internal.hpp"
 
@@ -33,6 +34,12 @@ static_assert(np::kFnDensity == MLX_FUNC_DENSITY && np::kFnDrhoDtemp == MLX_FUNC
                   np::kFnBeta == MLX_FUNC_BETA && np::kFnIbh == MLX_FUNC_IBH &&
                       np::kFnDensityRef == MLX_FUNC_DENSITY_REF,
               "func enum");
+
+static_assert(path::kGeneric == MLX_PATH_GENERIC && path::kFast == MLX_PATH_FAST &&
+                  path::kFastP3D == MLX_PATH_FAST_P3D && path::kAlignedT == MLX_PATH_ALIGNED_T &&
+                  path::kAlignedS == MLX_PATH_ALIGNED_S && path::kAlignedOut == MLX_PATH_ALIGNED_OUT &&
+                  path::kAlignedP == MLX_PATH_ALIGNED_P && path::kAlignedAll == MLX_PATH_ALIGNED_ALL,
+              "path codes");
 
 constexpr int kPromoteBlock = 256;
 
@@ -168,6 +175,8 @@ struct PromoteCall {
   hipStream_t st;
   bool is_f32;
   bool aligned16;  // every array operand and the result 16-byte aligned: several cells per thread
+  bool launch;     // false: mlx_path_eos_promote, which only wants is_f32 and width
+  int width;       // cells per lane (promote_width)
 };
 
 template <typename TT, typename TS, typename TP, int VEC>
@@ -177,19 +186,29 @@ void promote_launch(PromoteCall& c) {
                      c.st, c.T, c.S, c.p, c.eos, c.func, c.gravity, c.n, c.out);
 }
 
+// Cells per lane: the one rule, which promote_go launches by and mlx_path_eos_promote
+// (include/momlevel_path.h) reports.  `any_f64`: a float64 array among the operands (the result is
+// then float64 too): 2 cells = 16 bytes of it.  Float32 arrays and python floats only: 4 cells of a
+// float32 result, 2 of a float64 one (full_like(weak T)).
+inline int promote_width(bool any_f64, bool is_f32, bool aligned16) {
+  if (!aligned16) return 1;
+  if (any_f64) return 2;
+  return is_f32 ? 4 : 2;
+}
+
 template <typename TT, typename TS, typename TP>
 void promote_go(PromoteCall& c) {
   c.is_f32 = result_is_f32<TT, TS, TP>(c.eos, c.func);
-  // a float64 array among the operands (the result is then float64 too): 2 cells = 16 bytes of it
   constexpr bool ANY_F64 = std::is_same<TT, double>::value || std::is_same<TS, double>::value ||
                            std::is_same<TP, double>::value;
-  if (!c.aligned16) {
+  c.width = promote_width(ANY_F64, c.is_f32, c.aligned16);
+  if (!c.launch) return;  // the query: the types have answered
+  if (c.width == 1) {
     promote_launch<TT, TS, TP, 1>(c);
-  } else if constexpr (ANY_F64) {
+  } else if (c.width == 2) {
     promote_launch<TT, TS, TP, 2>(c);
-  } else {  // float32 arrays and python floats only
-    if (c.is_f32) promote_launch<TT, TS, TP, 4>(c);
-    else promote_launch<TT, TS, TP, 2>(c);  // (a float64 result of float32 operands: full_like(weak T))
+  } else if constexpr (!ANY_F64) {
+    promote_launch<TT, TS, TP, 4>(c);
   }
 }
 
@@ -205,6 +224,38 @@ void promote_s(PromoteCall& c, int kind_S, int kind_p) {
   if (kind_S == MLX_KIND_F64) promote_p<TT, double>(c, kind_p);
   else if (kind_S == MLX_KIND_F32) promote_p<TT, float>(c, kind_p);
   else promote_p<TT, np::Weak>(c, kind_p);
+}
+
+// by kinds: the template instantiation of the combination
+void promote_dispatch(PromoteCall& c, int kind_T, int kind_S, int kind_p) {
+  if (kind_T == MLX_KIND_F64) promote_s<double>(c, kind_S, kind_p);
+  else if (kind_T == MLX_KIND_F32) promote_s<float>(c, kind_S, kind_p);
+  else promote_s<np::Weak>(c, kind_S, kind_p);
+}
+
+// eos/linear.py never reads the pressure, except where it carries pso (the inverse barometer) or
+// the constant term of the rho_ref form: whatever was passed otherwise takes no part in the promotion
+inline bool promote_reads_p(int eos, int func) {
+  return eos == MLX_EOS_WRIGHT || func == MLX_FUNC_IBH || func == MLX_FUNC_DENSITY_REF;
+}
+
+// `bits`: MLX_PATH_ALIGNED_* of the result and of the operands (kind_p: of the pressure as it is
+// READ, MLX_KIND_WEAK where it is not).  Only arrays count; a python float has no address.
+inline bool promote_aligned(int bits, int kind_T, int kind_S, int kind_p) {
+  int need = MLX_PATH_ALIGNED_OUT;
+  if (kind_T != MLX_KIND_WEAK) need |= MLX_PATH_ALIGNED_T;
+  if (kind_S != MLX_KIND_WEAK) need |= MLX_PATH_ALIGNED_S;
+  if (kind_p != MLX_KIND_WEAK) need |= MLX_PATH_ALIGNED_P;
+  return (bits & need) == need;
+}
+
+int promote_check_enums(int eos, int func) {
+  if (eos != MLX_EOS_WRIGHT && eos != MLX_EOS_LINEAR) return detail::fail(MLX_E_ENUM, "unknown eos");
+  if (func < MLX_FUNC_DENSITY || func > MLX_FUNC_DENSITY_REF)
+    return detail::fail(MLX_E_ENUM, "unknown func");
+  if (func == MLX_FUNC_DENSITY_REF && eos != MLX_EOS_LINEAR)
+    return detail::fail(MLX_E_ENUM, "MLX_FUNC_DENSITY_REF is eos.linear.density's rho_ref form");
+  return 0;
 }
 
 // validates one operand and fills its launch record; `what` names it in the error text
@@ -248,24 +299,19 @@ extern "C" int mlx_eos_map_promote(const void* T, int kind_T, int64_t stride_T, 
                                    int64_t stride_p, int eos, int func, double gravity, int64_t n,
                                    void* out, int* out_kind, void* stream) {
   using namespace mlx;
-  if (eos != MLX_EOS_WRIGHT && eos != MLX_EOS_LINEAR) return detail::fail(MLX_E_ENUM, "unknown eos");
-  if (func < MLX_FUNC_DENSITY || func > MLX_FUNC_DENSITY_REF)
-    return detail::fail(MLX_E_ENUM, "unknown func");
-  if (func == MLX_FUNC_DENSITY_REF && eos != MLX_EOS_LINEAR)
-    return detail::fail(MLX_E_ENUM, "MLX_FUNC_DENSITY_REF is eos.linear.density's rho_ref form");
+  if (int rc = promote_check_enums(eos, func)) return rc;
   if (n <= 0) return detail::fail(MLX_E_SHAPE, "n must be > 0");
   if (n > ((int64_t)1 << 38)) return detail::fail(MLX_E_SHAPE, "n too large");
   if (!out || !out_kind) return detail::fail(MLX_E_NULL, "out and out_kind must not be NULL");
   if (reinterpret_cast<uintptr_t>(out) % 8) return detail::fail(MLX_E_ALIGN, "out not 8-byte aligned");
   PromoteCall c;
-  const bool p_read = (eos == MLX_EOS_WRIGHT) || func == MLX_FUNC_IBH || func == MLX_FUNC_DENSITY_REF;
+  const bool p_read = promote_reads_p(eos, func);
   if (int rc = promote_operand(T, kind_T, stride_T, "T", &c.T)) return rc;
   if (int rc = promote_operand(S, kind_S, stride_S, "S", &c.S)) return rc;
   if (p_read) {
     if (int rc = promote_operand(p, kind_p, stride_p, "p", &c.p)) return rc;
   } else {
-    // eos/linear.py never reads the pressure: whatever was passed (NULL included) is not touched and
-    // takes no part in the promotion
+    // whatever was passed (NULL included) is not touched
     static const double zero = 0.0;
     kind_p = MLX_KIND_WEAK;
     if (int rc = promote_operand(&zero, kind_p, 0, "p", &c.p)) return rc;
@@ -277,12 +323,36 @@ extern "C" int mlx_eos_map_promote(const void* T, int kind_T, int64_t stride_T, 
   c.out = out;
   c.st = static_cast<hipStream_t>(stream);
   c.is_f32 = false;
-  c.aligned16 = (reinterpret_cast<uintptr_t>(out) % 16) == 0;
-  for (const PromoteOperand* o : {&c.T, &c.S, &c.p})
-    if (o->ptr && o->stride == 1 && reinterpret_cast<uintptr_t>(o->ptr) % 16) c.aligned16 = false;
-  if (kind_T == MLX_KIND_F64) promote_s<double>(c, kind_S, kind_p);
-  else if (kind_T == MLX_KIND_F32) promote_s<float>(c, kind_S, kind_p);
-  else promote_s<np::Weak>(c, kind_S, kind_p);
+  c.launch = true;
+  c.width = 0;
+  int bits = (reinterpret_cast<uintptr_t>(out) % 16) == 0 ? MLX_PATH_ALIGNED_OUT : 0;
+  const PromoteOperand* ops[3] = {&c.T, &c.S, &c.p};
+  const int op_bit[3] = {MLX_PATH_ALIGNED_T, MLX_PATH_ALIGNED_S, MLX_PATH_ALIGNED_P};
+  for (int i = 0; i < 3; ++i)  // (one value for every cell: read as a scalar, wherever it lies)
+    if (!ops[i]->ptr || ops[i]->stride == 0 || reinterpret_cast<uintptr_t>(ops[i]->ptr) % 16 == 0)
+      bits |= op_bit[i];
+  c.aligned16 = promote_aligned(bits, kind_T, kind_S, kind_p);
+  promote_dispatch(c, kind_T, kind_S, kind_p);
   *out_kind = c.is_f32 ? MLX_KIND_F32 : MLX_KIND_F64;
   return detail::hip_status(hipGetLastError(), "mlx_eos_map_promote launch");
+}
+
+// include/momlevel_path.h: the same dispatch with the launch left out
+extern "C" int mlx_path_eos_promote(int kind_T, int kind_S, int kind_p, int eos, int func,
+                                    int aligned16, int* out_kind) {
+  using namespace mlx;
+  if (int rc = promote_check_enums(eos, func)) return rc;
+  if (!promote_reads_p(eos, func)) kind_p = MLX_KIND_WEAK;
+  for (int kind : {kind_T, kind_S, kind_p})
+    if (kind != MLX_KIND_F64 && kind != MLX_KIND_F32 && kind != MLX_KIND_WEAK)
+      return detail::fail(MLX_E_ENUM, "kinds must be MLX_KIND_F64, _F32 or _WEAK");
+  PromoteCall c{};
+  c.eos = eos;
+  c.func = func;
+  if (aligned16 & ~MLX_PATH_ALIGNED_ALL) return detail::fail(MLX_E_ENUM, "unknown bits in aligned16");
+  c.aligned16 = promote_aligned(aligned16, kind_T, kind_S, kind_p);
+  c.launch = false;
+  promote_dispatch(c, kind_T, kind_S, kind_p);
+  if (out_kind) *out_kind = c.is_f32 ? MLX_KIND_F32 : MLX_KIND_F64;
+  return c.width;
 }

@@ -183,6 +183,10 @@ static inline double linear_density(Val T, Val S) { /* eos/linear.py:55-56 */
 }
 static inline double eos_eval(int eos, int func, Val T, Val S, double p, double aux) {
   if (func == MLX_FUNC_IBH) {
+    /* float32 fields, linear EOS: rho_conv is float32 and the weak python floats keep
+     * rho_conv * gravity and -1.0 / (...) float32; pso widens the quotient */
+    if (eos == MLX_EOS_LINEAR && T.is_f32_faithful && S.is_f32_faithful)
+      return p * (double)(-1.0f / ((1000.0f + ((-0.2f * T.f) + (0.8f * S.f))) * (float)aux));
     const double rho = (eos == MLX_EOS_LINEAR) ? linear_density(T, S) : density(T, S, p);
     return p * (-1.0 / (rho * aux));
   }

@@ -16,6 +16,10 @@ records fit one tile a block and one launch a call.
     call of more records than one launch takes (core.vort_records_per_launch), so that a second
     launch starts at offsets of r0 whole planes.  Gates: vort_numpy on the records around the seam,
     and each side of it as a call of its own.
+  * eos_map_impl (csrc/momlevel_hip.hip), ``for (tb = 0; tb < nt; tb += L)`` with
+    ``t = t_base + blockIdx.z`` in k_eos_map: a record of more steps than one launch of the pointwise
+    EOS map takes (core.k0_path).  That walk-on is in test_gpu_eos_matrix.py
+    (test_k0_past_one_launch), beside the rest of that entry point's dispatch.
 
 Every size comes from the library's queries at run time, every test asserts from the query that
 the path was taken and prints the geometry.  Each result is written into a buffer that was filled
