@@ -7,7 +7,8 @@ detrend and deseason fits of ``trend``, and the grouped time statistics
 ``util.monthly_average`` / ``util.annual_cycle``, computed by hand-written HIP kernels behind a
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
-include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h).
+include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
+include/momlevel_quantile.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -39,6 +40,12 @@ runs behind K2 on a device scratch of ``delta_rho`` (include/momlevel_layer.h).
 against the actual time axis) are one NaN-aware banded operator along time with weight tables made
 on the host (include/momlevel_filter.h).
 
+``extremes`` (an EXTENSION too) gives the order statistics of a ``(time, ...)`` record where it
+lives: ``time_quantile`` / ``time_median`` (the values of xarray's ``.quantile(q, dim="time")``,
+over the whole record, per calendar month or per year) by radix select in registers, and
+``exceedance_count``, the steps above a number, a per-cell field or those quantiles
+(include/momlevel_quantile.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -50,6 +57,7 @@ __version__ = "0.1.0"
 from . import derived
 from . import dynamic
 from . import eos
+from . import extremes
 from . import filters
 from . import reference
 from . import regional
@@ -80,6 +88,7 @@ __all__ = [
     "dynamic",
     "inverse_barometer",
     "eos",
+    "extremes",
     "filters",
     "halosteric",
     "reference",

@@ -50,6 +50,8 @@ AREA_WINDOW = 32
 LAYER_MAX = 8
 # ---- constants mirrored from include/momlevel_filter.h -----------------------------
 FILTER_NORMALISE = 1
+# ---- constants mirrored from include/momlevel_quantile.h ----------------------------
+QUANTILE_MAX_Q = 8
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -221,6 +223,18 @@ FILTER_SIGNATURES = {
 }
 
 
+# The order statistics (include/momlevel_quantile.h): bound by load_quantile() on first use, for
+# the same reason.
+QUANTILE_SIGNATURES = {
+    "mlx_quantile_block_cells": (_i64, [_int]),
+    "mlx_quantile_unroll": (_i64, []),
+    "mlx_quantile_select": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp,
+                                   _vp]),
+    "mlx_quantile_exceed_count": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp,
+                                         _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -297,12 +311,13 @@ _GROUPS = {
     "layer": (LAYER_SIGNATURES, "the layer-integral kernel"),
     "filter": (FILTER_SIGNATURES, "the time-filter kernel"),
     "path": (PATH_SIGNATURES, "the path queries of the EOS maps"),
+    "quantile": (QUANTILE_SIGNATURES, "the quantile kernels"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
-_layer_bound = _filter_bound = _path_bound = False
+_layer_bound = _filter_bound = _path_bound = _quantile_bound = False
 
 
 def _load_group(group):
@@ -350,6 +365,10 @@ def load_filter():
 
 def load_path():
     return _load_group("path")
+
+
+def load_quantile():
+    return _load_group("quantile")
 
 
 def last_error():

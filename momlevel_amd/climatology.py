@@ -26,7 +26,7 @@ from . import cftime_lite
 from .cftime_lite import DatetimeLite
 from .labeled import _UNSUPPORTED, DataArray, Dataset, dtype_name, np_dtype
 
-__all__ = ["GroupPlan", "monthly_plan", "annual_cycle_plan", "grouped_stat"]
+__all__ = ["GroupPlan", "monthly_plan", "annual_cycle_plan", "yearly_plan", "grouped_stat"]
 
 STATS = ("mean", "std", "min", "max")
 
@@ -130,6 +130,20 @@ def annual_cycle_plan(time_da, tcoord="time", time_axis_year=None):
     year = int(time_axis_year) if time_axis_year is not None else mid_year(values[0], values[-1])
     members = [np.nonzero(months == mon)[0] for mon in range(1, 13)]
     return GroupPlan(members, _like_axis(month_midpoints(year, calendar), values[0]), tcoord)
+
+
+def yearly_plan(time_da, tcoord="time"):
+    """One group per calendar year present, in ascending order, with any number of steps per year
+    (a daily record, a year cut short); the new axis holds ``cftime_lite.year_midpoint`` of each
+    year.  EXTENSION: what ``extremes.time_quantile(..., by="year")`` goes by."""
+    values = _calendar_values(time_da, "yearly_plan")
+    calendar = values[0].calendar
+    years = np.array([t.year for t in values], dtype=np.int64)
+    present = sorted(set(years.tolist()))
+    members = [np.nonzero(years == yr)[0] for yr in present]
+    points = [cftime_lite._from_day_of_year(yr, cftime_lite.days_in_year(yr, calendar) / 2.0,
+                                            calendar) for yr in present]
+    return GroupPlan(members, _like_axis(points, values[0]), tcoord)
 
 
 def _check_record_dtype(da):

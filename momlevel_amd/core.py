@@ -1546,6 +1546,97 @@ def time_filter(y, w, lead, min_count=None, normalise=False, out=None, out_dtype
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# order statistics (include/momlevel_quantile.h; csrc/momlevel_quantile.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+def quantile_block_cells(dtype=torch.float64):
+    """Cells one block of the quantile kernels' pack path covers (mlx_quantile_block_cells)."""
+    return int(_lib.load_quantile().mlx_quantile_block_cells(_query_dtype(dtype)))
+
+
+def quantile_unroll():
+    """Rows of a group a lane of the quantile kernels has in flight (mlx_quantile_unroll)."""
+    return int(_lib.load_quantile().mlx_quantile_unroll())
+
+
+def quantile_levels(q):
+    """``q`` as the kernel takes it: a 1-D float64 host array of at least one level, each in
+    [0, 1]; or ``ValueError``.  Touches no device."""
+    try:
+        levels = np.asarray(q, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"q must be a number or a sequence of numbers in [0, 1], got {q!r}") from exc
+    if levels.ndim > 1 or levels.size < 1:
+        raise ValueError("q must be a number or a 1-D sequence of at least one number")
+    levels = np.ascontiguousarray(levels.reshape(-1))
+    if not np.all((levels >= 0.0) & (levels <= 1.0)):  # (false for NaN)
+        raise ValueError(f"every q must lie in [0, 1], got {q!r}")
+    return levels
+
+
+def _quantile_groups(nt, y, steps, offsets):
+    """(steps ptr, offsets ptr, nsel, ngroups, keep-alive) of a quantile call: a ``DeviceGroups``,
+    host lists (checked, uploaded), or None for all rows in order"""
+    if steps is None:
+        if offsets is not None:
+            raise ValueError("offsets without steps")
+        return None, None, nt, 1, None
+    if isinstance(steps, DeviceGroups):
+        groups = steps
+        if offsets is not None:
+            raise ValueError("a DeviceGroups carries its own offsets")
+        if groups.nt != nt or groups.steps.device != y.device:
+            raise ValueError("the groups were made for another record length or device")
+    else:
+        groups = DeviceGroups(steps, offsets, nt, y.device)
+    return _ptr(groups.steps), _ptr(groups.offsets), groups.nsel, groups.ngroups, groups
+
+
+def time_quantile(y, q, steps=None, offsets=None, out=None):
+    """NaN-skipping quantiles along the leading axis (mlx_quantile_select): y (nt, ...) float32 /
+    float64 on the device, ``q`` one level or a sequence of levels in [0, 1]  ->
+    (nq, ngroups, ...) of y's dtype.  Groups as in ``time_group_stat`` (host lists or a
+    ``DeviceGroups``); ``steps`` None: one group of all rows.  float64 results are value-identical
+    to ``numpy.nanquantile(y[sel], q, axis=0)`` (tests/quantile_numpy.py restates the contract);
+    float32 records are selected and interpolated in float64 and rounded once.  Any number of
+    levels: the kernel takes ``QUANTILE_MAX_Q`` a launch."""
+    require_device()
+    lib = _lib.load_quantile()
+    levels = quantile_levels(q)
+    y, nt, n, code = _time_record(y)
+    sp, op, nsel, ngroups, _keep = _quantile_groups(nt, y, steps, offsets)
+    shape = (int(levels.size), ngroups) + tuple(y.shape[1:])
+    out = _out_like(out, shape, y.dtype, y.device)
+    if n == 0:
+        return out
+    for c0 in range(0, levels.size, _lib.QUANTILE_MAX_Q):
+        chunk = np.ascontiguousarray(levels[c0:c0 + _lib.QUANTILE_MAX_Q])
+        _call(lib, "mlx_quantile_select", y.device, _ptr(y), code, sp, op, nsel, ngroups, nt, n,
+              chunk.ctypes.data, int(chunk.size), _ptr(out[c0:c0 + chunk.size]))
+    return out
+
+
+def time_exceed_count(y, thr, steps=None, offsets=None):
+    """Steps of each group with ``y > thr`` (mlx_quantile_exceed_count): strict, compared in
+    float64, a NaN on either side counts nothing.  y (nt, ...) float32 / float64 on the device,
+    ``thr`` (ngroups, ...) (any float dtype, used as float64), groups as in ``time_quantile``  ->
+    (ngroups, ...) int64."""
+    require_device()
+    lib = _lib.load_quantile()
+    y, nt, n, code = _time_record(y)
+    sp, op, nsel, ngroups, _keep = _quantile_groups(nt, y, steps, offsets)
+    shape = (ngroups,) + tuple(y.shape[1:])
+    thr = _f64(thr, y.device)
+    if tuple(thr.shape) != shape:
+        raise ValueError(f"thr must have shape {shape} (one row per group), got {tuple(thr.shape)}")
+    out = torch.empty(shape, dtype=torch.int64, device=y.device)
+    if n == 0:
+        return out
+    _call(lib, "mlx_quantile_exceed_count", y.device, _ptr(y), code, sp, op, nsel, ngroups, nt, n,
+          _ptr(thr), _ptr(out))
+    return out
+
+
 def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
     """derived.calc_dz core on device -> (nz, ny, nx)."""
     require_device()

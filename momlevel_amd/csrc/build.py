@@ -29,6 +29,8 @@ FEATURES = {
     "area": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_area.h"],
     "layer": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_layer.h"],
     "filter": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_filter.h"],
+    "quantile": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp",
+                 "include/momlevel_quantile.h"],
 }
 
 
@@ -136,6 +138,11 @@ def layer_source_sha():
 def filter_source_sha():
     """the time-filter kernel's own guard: csrc/momlevel_filter.hip (+ what it includes, + flags)"""
     return feature_source_sha("filter")
+
+
+def quantile_source_sha():
+    """the quantile kernels' own guard: csrc/momlevel_quantile.hip (+ what it includes, + flags)"""
+    return feature_source_sha("quantile")
 
 
 def hipcc():
