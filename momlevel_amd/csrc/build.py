@@ -21,15 +21,19 @@ _TIMED_UNITS = ["momlevel_hip.hip", "momlevel_promote.hip"]
 # hashes them.  One row per feature: SOURCES, DEPENDS and <feature>_source_sha() follow.
 FEATURES = {
     "strat": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp"],
-    "trend": ["eos_device.hpp", "mlx_internal.hpp", "include/momlevel_trend.h"],
-    "clim": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_clim.h"],
-    "gauge": ["eos_device.hpp", "mlx_internal.hpp", "include/momlevel_gauge.h"],
-    "spice": ["mlx_internal.hpp", "include/momlevel_spice.h"],
-    "vort": ["mlx_internal.hpp", "include/momlevel_vort.h"],
+    "trend": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
+              "include/momlevel_trend.h"],
+    "clim": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
+             "include/momlevel_clim.h"],
+    "gauge": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
+              "include/momlevel_gauge.h"],
+    "spice": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_spice.h"],
+    "vort": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_vort.h"],
     "area": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_area.h"],
     "layer": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_layer.h"],
-    "filter": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_filter.h"],
-    "quantile": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp",
+    "filter": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
+               "include/momlevel_filter.h"],
+    "quantile": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
                  "include/momlevel_quantile.h"],
 }
 

@@ -1,11 +1,21 @@
 // Shared by feature translation units of libmomlevel_hip.so: a pack of adjacent cells that moves in
 // one memory instruction, and the operand checks of their entry points.  Nothing here is part of the
-// C ABI.  Included by momlevel_strat.hip and momlevel_clim.hip, whose kernels compile to the
-// instructions they had with their private copies.  (momlevel_hip.hip keeps its own load_pack: its
-// sources are the ones whose hash guards the committed steric profiles.  The trend, gauge, spice
-// and vort units keep theirs until a GPU visit times them: moving them changes their code -- the
-// `double` spelling of a float32 pair there costs LDS and the `nt` policy -- and their hashes, which
-// the committed logs under profiles/ quote.)
+// C ABI.  Every feature unit but momlevel_trend.hip takes its pack I/O from here (mlx_record.hpp
+// adds what the (time, cells) record units share on top; momlevel_gauge.hip uses the host checks):
+//   strat, clim, area, layer, filter, quantile, spice: the instructions of a private copy.
+//   vort: 18 of its 36 kernels changed with the move.  The private copy loaded a float32 pair as one
+//     `double`, which in the mixed-dtype kernels went through 4 to 12 KiB of LDS; on load_pack they
+//     use none and up to 6 VGPRs fewer.  Timed against the parent's library on one MI355X
+//     (profiles/record_fold_ab.log; scripts/bench_vort.py, alternating processes): no case slower
+//     than the parent's slowest round, the 14 mixed-dtype cases 3 to 17 % faster.
+//   trend: keeps its own TPack / tload / tstore.  On load_pack / store_pack 16 float32 kernels
+//     changed and the two-cell ones measured slower in the same log (1200 x 1081 x 1442, float32,
+//     median against the parent's slowest round): k_time_linfit 1.62-1.65 ms against 1.53,
+//     k_time_project<6> 1.68-1.70 against 1.60, k_time_apply remove 5.48-5.49 against 5.40; model_resid
+//     5.56 against 5.59 passed.  The private `double` spelling of a float32 pair loses the `nt`
+//     policy on the loads of the unrolled fit loop, and that is the faster code.
+//   momlevel_hip.hip keeps its own load_pack: its sources are the ones whose hash guards the
+//     committed steric profiles, and the move changes 228 of its 473 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

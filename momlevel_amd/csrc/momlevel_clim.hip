@@ -31,9 +31,7 @@
 
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_clim.h"
-#include "eos_device.hpp"
-#include "mlx_internal.hpp"
-#include "mlx_pack.hpp"
+#include "mlx_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,28 +42,11 @@ constexpr int kClimBlock = 256;  // 4 waves of 64
 constexpr int kClimUnroll = 8;   // row packs a lane has in flight
 constexpr unsigned kClimMaxGridY = 65535;
 
-// The row of step index s, widened to float64.  s is wave-uniform.  An index outside [0, nt) --
-// a caller's mistake the entry point cannot see -- reads row 0 and yields NaN: never out of bounds.
-template <typename TIn, int V>
-struct Row {
-  Pack<TIn, V> raw;
-  bool ok;
-  __device__ __forceinline__ double at(int k) const {
-    return ok ? (double)raw.v[k] : canonical_nan();  // float32 -> float64 is exact
-  }
-};
-
-template <typename TIn, int V>
-__device__ __forceinline__ Row<TIn, V> row_load(const TIn* __restrict__ ycol, int32_t s, int64_t nt,
-                                                int64_t n) {
-  Row<TIn, V> r;
-  r.ok = (uint32_t)s < (uint32_t)nt;
-  r.raw = load_pack<TIn, V, true>(ycol + (int64_t)(r.ok ? s : 0) * n);
-  return r;
-}
-
 // Visit the rows steps[lo .. hi) in order: kClimUnroll loads are issued before the first of them
-// is consumed, and the next batch of step indices is fetched before the loads of this one.
+// is consumed, and the next batch of step indices is fetched before the loads of this one.  Rows
+// move with the `nt` policy (a group is read once, twice for STD) and every index is tested.
+// (momlevel_quantile.hip's walk_rows is another loop -- no index prefetch, a hook after each batch,
+// a mode without a list -- and one loop for both would branch on its caller.)
 template <typename TIn, int V, typename F>
 __device__ __forceinline__ void walk_group(const TIn* __restrict__ ycol,
                                            const int32_t* __restrict__ steps, int64_t lo, int64_t hi,
@@ -83,14 +64,14 @@ __device__ __forceinline__ void walk_group(const TIn* __restrict__ ycol,
       for (int u = 0; u < U; ++u) nxt[u] = steps[ahead + u];
       Row<TIn, V> r[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) r[u] = row_load<TIn, V>(ycol, cur[u], nt, n);
+      for (int u = 0; u < U; ++u) r[u] = row_load<TIn, V, true, true>(ycol, cur[u], nt, n);
 #pragma unroll
       for (int u = 0; u < U; ++u) consume(r[u]);
 #pragma unroll
       for (int u = 0; u < U; ++u) cur[u] = nxt[u];
     }
   }
-  for (; j < hi; ++j) consume(row_load<TIn, V>(ycol, steps[j], nt, n));
+  for (; j < hi; ++j) consume(row_load<TIn, V, true, true>(ycol, steps[j], nt, n));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -106,9 +87,8 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
   if (i >= n) return;
   const TIn* ycol = y + i;
   for (int64_t g = blockIdx.y; g < ngroups; g += gridDim.y) {
-    int64_t lo = offsets[g], hi = offsets[g + 1];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > nsel ? nsel : hi;
+    int64_t lo, hi;
+    group_bounds(offsets, g, nsel, lo, hi);
     double res[V];
     if constexpr (STAT == MLX_STAT_MEAN || STAT == MLX_STAT_STD) {
       // -0.0 + x is x for every x, and -0.0 + (+0.0) is +0.0: the sum starts as the first step's
@@ -161,13 +141,7 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
     }
     Pack<TIn, V> o;
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if constexpr (sizeof(TIn) == 8) {
-        o.v[k] = is_nan(res[k]) ? canonical_nan() : res[k];
-      } else {
-        o.v[k] = is_nan(res[k]) ? canonical_nan_f32() : (float)res[k];  // the one rounding
-      }
-    }
+    for (int k = 0; k < V; ++k) o.v[k] = narrow<TIn>(res[k], is_nan(res[k]));
     store_pack<TIn, V, false>(out + g * n + i, o);
   }
 }
@@ -177,9 +151,6 @@ __global__ __launch_bounds__(kClimBlock) void k_group_stat(const TIn* __restrict
 // ------------------------------------------------------------------------------------------
 using detail::fail;
 using detail::hip_status;
-
-constexpr int64_t kMaxCells = (int64_t)1 << 38;
-constexpr int64_t kMaxSteps = (int64_t)1 << 31;
 
 template <typename TIn, int V, int STAT>
 int launch_stat(const void* y, const int32_t* steps, const int64_t* offsets, int64_t nsel,
@@ -218,30 +189,16 @@ int mlx_clim_group_stat(const void* y, int dtype, const int32_t* steps, const in
                         void* stream) {
   if (!y || !steps || !offsets || !out)
     return fail(MLX_E_NULL, "y, steps, offsets, out must not be NULL");
-  if (!is_float_dtype(dtype)) return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
   if (stat < MLX_STAT_MEAN || stat > MLX_STAT_MAX) return fail(MLX_E_ENUM, "unknown MLX_STAT_* stat");
-  int64_t total, rows;
-  if (nt <= 0 || n <= 0 || nsel <= 0 || ngroups <= 0 || nt >= kMaxSteps || nsel >= kMaxSteps ||
-      n > kMaxCells || __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
-      __builtin_mul_overflow(ngroups, n, &rows) || rows > INT64_MAX / 64 ||
-      ceil_div(n, kClimBlock) > 2147483647LL)
-    return fail(MLX_E_SHAPE,
-                "need 0 < nt, nsel < 2^31, ngroups > 0, 0 < n <= 2^38, nt*n and ngroups*n addressable");
+  if (int rc = check_grouped(y, dtype, steps, offsets, nsel, ngroups, nt, n, 1)) return rc;
   const size_t elem = dtype_size(dtype);
-  if (!aligned(y, elem) || !aligned(out, elem)) return fail(MLX_E_ALIGN, "y / out not element-aligned");
-  if (!aligned(steps, 4) || !aligned(offsets, 8))
-    return fail(MLX_E_ALIGN, "steps not 4-byte or offsets not 8-byte aligned");
+  if (!aligned(out, elem)) return fail(MLX_E_ALIGN, "out not element-aligned");
   hipStream_t st = (hipStream_t)stream;
-  // cells per lane: the widest pack (16 bytes at most) that divides every row and keeps every row
-  // of the record and of the result pack-aligned
-  int v = (int)(16 / elem);
-  while (v > 1 && (n % v || !aligned(y, elem * v) || !aligned(out, elem * v))) v /= 2;
-  if (dtype == MLX_DTYPE_F64)
-    return v == 2 ? launch_any<double, 2>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
-                  : launch_any<double, 1>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st);
-  return v == 4   ? launch_any<float, 4>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
-         : v == 2 ? launch_any<float, 2>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st)
-                  : launch_any<float, 1>(stat, y, steps, offsets, nsel, ngroups, nt, n, out, st);
+  const int v = pack_width(n, elem, {{y, elem}, {out, elem}});
+  return dispatch_pack(dtype, v, [&](auto t, auto w) {
+    return launch_any<typename decltype(t)::type, decltype(w)::value>(stat, y, steps, offsets, nsel,
+                                                                      ngroups, nt, n, out, st);
+  });
 }
 
 }  // extern "C"

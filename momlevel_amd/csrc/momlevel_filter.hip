@@ -38,9 +38,7 @@
 
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_filter.h"
-#include "eos_device.hpp"
-#include "mlx_internal.hpp"
-#include "mlx_pack.hpp"
+#include "mlx_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -54,7 +52,8 @@ constexpr unsigned kFilterMaxGridY = 65535;
 constexpr int64_t kFilterTargetBlocks = 8192;  // blocks a launch aims at before it stops cutting time
 
 // The row of step s, widened to float64; a step outside [0, nt) is a NaN row and is not loaded.
-// s is wave-uniform.
+// s is wave-uniform.  (Not mlx_record.hpp's Row: that one loads row 0 for such a step, and here the
+// steps before and after the record are the ordinary case, at every edge tile.)
 template <typename TIn, int V>
 struct FRow {
   Pack<TIn, V> raw;
@@ -175,12 +174,7 @@ __global__ __launch_bounds__(kFilterBlock) void k_time_filter(
 #pragma unroll
         for (int c = 0; c < V; ++c) {
           double res = NORM ? a.acc[r][c] / a.ws[r][c] : a.acc[r][c];
-          const bool nan = a.cnt[r][c] < min_count || is_nan(res);
-          if constexpr (sizeof(TOut) == 8) {
-            o.v[c] = nan ? canonical_nan() : res;
-          } else {
-            o.v[c] = nan ? canonical_nan_f32() : (float)res;  // the one rounding
-          }
+          o.v[c] = narrow<TOut>(res, a.cnt[r][c] < min_count || is_nan(res));
         }
         store_pack<TOut, V, true>(out + (int64_t)(t0 + r) * n + i, o);
       }
@@ -194,7 +188,6 @@ __global__ __launch_bounds__(kFilterBlock) void k_time_filter(
 using detail::fail;
 using detail::hip_status;
 
-constexpr int64_t kMaxCells = (int64_t)1 << 38;
 constexpr int64_t kMaxSteps = (int64_t)1 << 30;  // (t - lead + k stays inside int32)
 
 struct FilterArgs {
@@ -207,14 +200,6 @@ struct FilterArgs {
   void* out;
   hipStream_t st;
 };
-
-// the record extents mlx_filter_apply takes
-inline bool filter_shape_ok(int64_t nt, int64_t n) {
-  int64_t total;
-  return !(nt <= 0 || n <= 0 || nt >= kMaxSteps || n > kMaxCells ||
-           __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
-           ceil_div(n, kFilterBlock) > 2147483647LL);
-}
 
 // Consecutive time tiles a block walks (the kernel's `per`) for v cells a lane: the one rule, which
 // mlx_filter_tiles_per_block reports and launch_filter launches by.
@@ -244,14 +229,6 @@ int launch_norm(bool norm, const FilterArgs& a) {
   return norm ? launch_filter<TIn, TOut, V, true>(a) : launch_filter<TIn, TOut, V, false>(a);
 }
 
-template <typename TIn, typename TOut>
-int launch_width(int v, bool norm, const FilterArgs& a) {
-  if constexpr (sizeof(TIn) == 4) {
-    if (v == 4) return launch_norm<TIn, TOut, 4>(norm, a);
-  }
-  return v >= 2 ? launch_norm<TIn, TOut, 2>(norm, a) : launch_norm<TIn, TOut, 1>(norm, a);
-}
-
 }  // namespace
 }  // namespace mlx
 
@@ -269,7 +246,7 @@ int64_t mlx_filter_window_edge(int i) {
 }
 
 int64_t mlx_filter_tiles_per_block(int64_t nt, int64_t n, int cells_per_lane) {
-  if (!filter_shape_ok(nt, n)) return 0;
+  if (!record_fits(nt, n, kMaxSteps)) return 0;
   if (cells_per_lane != 1 && cells_per_lane != 2 && cells_per_lane != 4) return 0;
   if (n % cells_per_lane != 0) return 0;  // (no launch has lanes that wide)
   return filter_tiles_per_block(nt, n, cells_per_lane);
@@ -282,7 +259,7 @@ int mlx_filter_apply(const void* y, int dtype, const double* w, int64_t W, int64
   if (!is_float_dtype(dtype) || !is_float_dtype(out_dtype))
     return fail(MLX_E_ENUM, "dtype and out_dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
   if (flags & ~MLX_FILTER_NORMALISE) return fail(MLX_E_ENUM, "unknown MLX_FILTER_* flag");
-  if (!filter_shape_ok(nt, n))
+  if (!record_fits(nt, n, kMaxSteps))
     return fail(MLX_E_SHAPE, "need 0 < nt < 2^30, 0 < n <= 2^38, nt*n addressable");
   if (W < 1 || W > nt) return fail(MLX_E_SHAPE, "need 1 <= W <= nt");
   if (lead < 0 || lead >= W) return fail(MLX_E_SHAPE, "need 0 <= lead < W");
@@ -291,22 +268,16 @@ int mlx_filter_apply(const void* y, int dtype, const double* w, int64_t W, int64
   const size_t elem = dtype_size(dtype), oelem = dtype_size(out_dtype);
   if (!aligned(y, elem) || !aligned(out, oelem)) return fail(MLX_E_ALIGN, "y / out not element-aligned");
   if (!aligned(w, 8)) return fail(MLX_E_ALIGN, "w not 8-byte aligned");
-  // cells per lane: the widest pack (16 bytes of y at most) that divides every row and keeps every
-  // row of the record and of the result aligned to its access (a 32-byte result pack: two of 16)
-  int v = (int)(16 / elem);
-  while (v > 1) {
-    const size_t oacc = oelem * v > 16 ? 16 : oelem * v;
-    if (n % v == 0 && aligned(y, elem * v) && aligned(out, oacc)) break;
-    v /= 2;
-  }
+  const int v = pack_width(n, elem, {{y, elem}, {out, oelem}});
   const FilterArgs a{y, w, (int32_t)W, w_stride, (int32_t)lead, (int32_t)min_count, (int32_t)nt, n,
                      out, (hipStream_t)stream};
   const bool norm = (flags & MLX_FILTER_NORMALISE) != 0;
-  if (dtype == MLX_DTYPE_F64)
-    return out_dtype == MLX_DTYPE_F64 ? launch_width<double, double>(v, norm, a)
-                                      : launch_width<double, float>(v, norm, a);
-  return out_dtype == MLX_DTYPE_F64 ? launch_width<float, double>(v, norm, a)
-                                    : launch_width<float, float>(v, norm, a);
+  return dispatch_pack(dtype, v, [&](auto t, auto width) {
+    typedef typename decltype(t)::type TIn;
+    constexpr int V = decltype(width)::value;
+    return out_dtype == MLX_DTYPE_F64 ? launch_norm<TIn, double, V>(norm, a)
+                                      : launch_norm<TIn, float, V>(norm, a);
+  });
 }
 
 }  // extern "C"

@@ -33,8 +33,7 @@
 
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_gauge.h"
-#include "eos_device.hpp"
-#include "mlx_internal.hpp"
+#include "mlx_record.hpp"  // (the host checks: aligned, ceil_div, kMaxCells)
 
 #pragma clang fp contract(off)
 
@@ -245,10 +244,6 @@ __global__ __launch_bounds__(kPrepBlock) void k_gauge_gather(const U* __restrict
 using detail::fail;
 using detail::hip_status;
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b != 0); }
-
-constexpr int64_t kMaxCells = (int64_t)1 << 38;
 constexpr int64_t kMaxGauges = (int64_t)1 << 31;
 constexpr int64_t kMaxChunk = (int64_t)1 << 30;  // the winner's offset in its part is an int32
 constexpr int64_t kWantBlocks = 8192;            // one-wave blocks: 8 per SIMD of 256 CUs

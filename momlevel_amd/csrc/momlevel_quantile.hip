@@ -36,9 +36,7 @@
 
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_quantile.h"
-#include "eos_device.hpp"
-#include "mlx_internal.hpp"
-#include "mlx_pack.hpp"
+#include "mlx_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -85,27 +83,12 @@ struct Key<float> {
   }
 };
 
-// The row of step index s.  s is wave-uniform.  An index outside [0, nt) -- a caller's mistake the
-// entry point cannot see -- reads row 0 and counts as a NaN step: never out of bounds.
-template <typename TIn, int V>
-struct Row {
-  Pack<TIn, V> raw;
-  bool ok;
-  __device__ __forceinline__ bool valid(int k) const { return ok && raw.v[k] == raw.v[k]; }
-};
-
-template <typename TIn, int V, bool LISTED>
-__device__ __forceinline__ Row<TIn, V> row_load(const TIn* __restrict__ ycol, int32_t s, int64_t nt,
-                                                int64_t n) {
-  Row<TIn, V> r;
-  r.ok = LISTED ? (uint32_t)s < (uint32_t)nt : true;  // (unlisted: s walks [0, nt) itself)
-  r.raw = load_pack<TIn, V, false>(ycol + (int64_t)(r.ok ? s : 0) * n);
-  return r;
-}
-
 // Visit the rows steps[lo .. hi) (LISTED) or lo .. hi themselves: kQuantUnroll loads are issued
 // before the first of them is consumed.  after_batch() runs once at least every kQuantUnroll rows
-// and after the last one.  The order does not matter to a count.
+// and after the last one.  The order does not matter to a count.  Rows stay cached: every pass
+// reads them again.  Unlisted, s walks [0, nt) itself and is not tested.
+// (momlevel_clim.hip's walk_group is another loop -- it prefetches the next batch of indices and
+// has neither the hook nor the unlisted mode -- and one loop for both would branch on its caller.)
 template <typename TIn, int V, bool LISTED, typename F, typename B>
 __device__ __forceinline__ void walk_rows(const TIn* __restrict__ ycol,
                                           const int32_t* __restrict__ steps, int64_t lo, int64_t hi,
@@ -118,25 +101,22 @@ __device__ __forceinline__ void walk_rows(const TIn* __restrict__ ycol,
     for (int u = 0; u < U; ++u) s[u] = LISTED ? steps[j + u] : (int32_t)(j + u);
     Row<TIn, V> r[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) r[u] = row_load<TIn, V, LISTED>(ycol, s[u], nt, n);
+    for (int u = 0; u < U; ++u) r[u] = row_load<TIn, V, false, LISTED>(ycol, s[u], nt, n);
 #pragma unroll
     for (int u = 0; u < U; ++u) consume(r[u]);
     after_batch();
   }
   for (; j < hi; ++j)
-    consume(row_load<TIn, V, LISTED>(ycol, LISTED ? steps[j] : (int32_t)j, nt, n));
+    consume(row_load<TIn, V, false, LISTED>(ycol, LISTED ? steps[j] : (int32_t)j, nt, n));
   after_batch();
 }
 
-// the bounds of group g, clamped to the list
+// the bounds of group g: clamped to the list, or every row
 template <bool LISTED>
-__device__ __forceinline__ void group_bounds(const int64_t* __restrict__ offsets, int64_t g,
-                                             int64_t nsel, int64_t nt, int64_t& lo, int64_t& hi) {
+__device__ __forceinline__ void group_rows(const int64_t* __restrict__ offsets, int64_t g,
+                                           int64_t nsel, int64_t nt, int64_t& lo, int64_t& hi) {
   if constexpr (LISTED) {
-    lo = offsets[g];
-    hi = offsets[g + 1];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > nsel ? nsel : hi;
+    group_bounds(offsets, g, nsel, lo, hi);
   } else {
     lo = 0;
     hi = nt;
@@ -179,7 +159,7 @@ __global__ __launch_bounds__(kQuantBlock) void k_quantile_select(
   for (int j = 1; j < MLX_QUANTILE_MAX_Q; ++j) q = qi == j ? qs.v[j] : q;
   for (int64_t g = blockIdx.z; g < ngroups; g += gridDim.z) {
     int64_t lo, hi;
-    group_bounds<LISTED>(offsets, g, nsel, nt, lo, hi);
+    group_rows<LISTED>(offsets, g, nsel, nt, lo, hi);
     K prefix[V];
     uint32_t rank[V], c[V];
 #pragma unroll
@@ -282,12 +262,7 @@ __global__ __launch_bounds__(kQuantBlock) void k_quantile_select(
       const double d = b - a;
       double res = a + d * gam;
       if (gam >= 0.5) res = b - d * (1.0 - gam);
-      const bool nan = c[k] == 0 || is_nan(res);
-      if constexpr (sizeof(TIn) == 8) {
-        o.v[k] = nan ? canonical_nan() : res;
-      } else {
-        o.v[k] = nan ? canonical_nan_f32() : (float)res;  // the one rounding
-      }
+      o.v[k] = narrow<TIn>(res, c[k] == 0 || is_nan(res));
     }
     store_pack<TIn, V, false>(out + ((int64_t)qi * ngroups + g) * n + i, o);
   }
@@ -306,7 +281,7 @@ __global__ __launch_bounds__(kQuantBlock) void k_exceed_count(
   const TIn* ycol = y + i;
   for (int64_t g = blockIdx.z; g < ngroups; g += gridDim.z) {
     int64_t lo, hi;
-    group_bounds<LISTED>(offsets, g, nsel, nt, lo, hi);
+    group_rows<LISTED>(offsets, g, nsel, nt, lo, hi);
     const Pack<double, V> t = load_pack<double, V, false>(thr + g * n + i);
     Pack<int64_t, V> cnt;
 #pragma unroll
@@ -325,9 +300,6 @@ __global__ __launch_bounds__(kQuantBlock) void k_exceed_count(
 // ------------------------------------------------------------------------------------------
 using detail::fail;
 using detail::hip_status;
-
-constexpr int64_t kMaxCells = (int64_t)1 << 38;
-constexpr int64_t kMaxSteps = (int64_t)1 << 31;
 
 dim3 quant_grid(int64_t n, int v, int nq, int64_t ngroups) {
   const unsigned gz = ngroups < (int64_t)kQuantMaxGridZ ? (unsigned)ngroups : kQuantMaxGridZ;
@@ -362,30 +334,6 @@ int launch_exceed(const void* y, const int32_t* steps, const int64_t* offsets, i
   return hip_status(hipGetLastError(), "k_exceed_count launch");
 }
 
-// what both entry points refuse alike; `rows` result rows of n cells
-int check_record(const void* y, int dtype, const int32_t* steps, const int64_t* offsets,
-                 int64_t nsel, int64_t ngroups, int64_t nt, int64_t n, int64_t rows_per_group) {
-  if (!y) return fail(MLX_E_NULL, "y must not be NULL");
-  if ((steps == nullptr) != (offsets == nullptr))
-    return fail(MLX_E_NULL, "steps and offsets must both be given or both be NULL");
-  if (!steps && ngroups != 1)
-    return fail(MLX_E_NULL, "NULL steps / offsets mean one group of all rows: ngroups must be 1");
-  if (!is_float_dtype(dtype)) return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
-  int64_t total, rows;
-  if (nt <= 0 || n <= 0 || nsel <= 0 || ngroups <= 0 || nt >= kMaxSteps || nsel >= kMaxSteps ||
-      n > kMaxCells || __builtin_mul_overflow(nt, n, &total) || total > INT64_MAX / 64 ||
-      __builtin_mul_overflow(ngroups, n, &rows) || rows > INT64_MAX / (64 * rows_per_group) ||
-      ceil_div(n, kQuantBlock) > 2147483647LL)
-    return fail(MLX_E_SHAPE,
-                "need 0 < nt, nsel < 2^31, ngroups > 0, 0 < n <= 2^38, nt*n and the result addressable");
-  if (!steps && nsel != nt)
-    return fail(MLX_E_SHAPE, "NULL steps / offsets list every row: nsel must equal nt");
-  if (!aligned(y, dtype_size(dtype))) return fail(MLX_E_ALIGN, "y not element-aligned");
-  if (steps && (!aligned(steps, 4) || !aligned(offsets, 8)))
-    return fail(MLX_E_ALIGN, "steps not 4-byte or offsets not 8-byte aligned");
-  return 0;
-}
-
 }  // namespace
 }  // namespace mlx
 
@@ -405,7 +353,7 @@ int mlx_quantile_select(const void* y, int dtype, const int32_t* steps, const in
   if (!q || !out) return fail(MLX_E_NULL, "q, out must not be NULL");
   if (nq < 1 || nq > MLX_QUANTILE_MAX_Q)
     return fail(MLX_E_SHAPE, "nq must lie in [1, MLX_QUANTILE_MAX_Q]");
-  if (int rc = check_record(y, dtype, steps, offsets, nsel, ngroups, nt, n, nq)) return rc;
+  if (int rc = check_grouped(y, dtype, steps, offsets, nsel, ngroups, nt, n, nq)) return rc;
   QList qs;
   for (int j = 0; j < MLX_QUANTILE_MAX_Q; ++j) {
     qs.v[j] = j < nq ? q[j] : 0.0;
@@ -414,35 +362,27 @@ int mlx_quantile_select(const void* y, int dtype, const int32_t* steps, const in
   const size_t elem = dtype_size(dtype);
   if (!aligned(out, elem)) return fail(MLX_E_ALIGN, "out not element-aligned");
   hipStream_t st = (hipStream_t)stream;
-  // cells per lane: the widest pack (16 bytes at most) that divides every row and keeps every row
-  // of the record and of the result pack-aligned
-  int v = (int)(16 / elem);
-  while (v > 1 && (n % v || !aligned(y, elem * v) || !aligned(out, elem * v))) v /= 2;
-  if (dtype == MLX_DTYPE_F64)
-    return v == 2 ? launch_select<double, 2>(y, steps, offsets, nsel, ngroups, nt, n, qs, nq, out, st)
-                  : launch_select<double, 1>(y, steps, offsets, nsel, ngroups, nt, n, qs, nq, out, st);
-  return v == 4   ? launch_select<float, 4>(y, steps, offsets, nsel, ngroups, nt, n, qs, nq, out, st)
-         : v == 2 ? launch_select<float, 2>(y, steps, offsets, nsel, ngroups, nt, n, qs, nq, out, st)
-                  : launch_select<float, 1>(y, steps, offsets, nsel, ngroups, nt, n, qs, nq, out, st);
+  const int v = pack_width(n, elem, {{y, elem}, {out, elem}});
+  return dispatch_pack(dtype, v, [&](auto t, auto w) {
+    return launch_select<typename decltype(t)::type, decltype(w)::value>(y, steps, offsets, nsel,
+                                                                         ngroups, nt, n, qs, nq, out, st);
+  });
 }
 
 int mlx_quantile_exceed_count(const void* y, int dtype, const int32_t* steps,
                               const int64_t* offsets, int64_t nsel, int64_t ngroups, int64_t nt,
                               int64_t n, const double* thr, int64_t* out, void* stream) {
   if (!thr || !out) return fail(MLX_E_NULL, "thr, out must not be NULL");
-  if (int rc = check_record(y, dtype, steps, offsets, nsel, ngroups, nt, n, 1)) return rc;
+  if (int rc = check_grouped(y, dtype, steps, offsets, nsel, ngroups, nt, n, 1)) return rc;
   if (!aligned(thr, 8) || !aligned(out, 8)) return fail(MLX_E_ALIGN, "thr / out not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const size_t elem = dtype_size(dtype);
-  // the threshold and the counts move in 16-byte accesses once a lane holds two cells or more
-  int v = (int)(16 / elem);
-  while (v > 1 && (n % v || !aligned(y, elem * v) || !aligned(thr, 16) || !aligned(out, 16))) v /= 2;
-  if (dtype == MLX_DTYPE_F64)
-    return v == 2 ? launch_exceed<double, 2>(y, steps, offsets, nsel, ngroups, nt, n, thr, out, st)
-                  : launch_exceed<double, 1>(y, steps, offsets, nsel, ngroups, nt, n, thr, out, st);
-  return v == 4   ? launch_exceed<float, 4>(y, steps, offsets, nsel, ngroups, nt, n, thr, out, st)
-         : v == 2 ? launch_exceed<float, 2>(y, steps, offsets, nsel, ngroups, nt, n, thr, out, st)
-                  : launch_exceed<float, 1>(y, steps, offsets, nsel, ngroups, nt, n, thr, out, st);
+  // (the threshold and the counts are 8-byte cells: accesses of 16 once a lane holds two or more)
+  const int v = pack_width(n, elem, {{y, elem}, {thr, 8}, {out, 8}});
+  return dispatch_pack(dtype, v, [&](auto t, auto w) {
+    return launch_exceed<typename decltype(t)::type, decltype(w)::value>(y, steps, offsets, nsel,
+                                                                         ngroups, nt, n, thr, out, st);
+  });
 }
 
 }  // extern "C"

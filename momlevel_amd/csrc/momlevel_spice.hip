@@ -31,6 +31,7 @@
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_spice.h"
 #include "mlx_internal.hpp"
+#include "mlx_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,8 +42,6 @@ constexpr int kSpiceBlock = 256;  // 4 waves of 64
 constexpr int kSpiceU = 2;        // packs per thread and field in flight
 constexpr int64_t kSpiceMaxBlocks = (int64_t)1 << 23;
 constexpr int64_t kSpiceMaxCells = (int64_t)1 << 38;
-
-typedef float spice_f4 __attribute__((ext_vector_type(4)));
 
 // Flament (2002), table 1: the coefficient of theta^j (S - 35)^k, here one ROW PER POWER OF
 // (S - 35) -- the order the nested scheme consumes them in.  Compile-time constants: after
@@ -74,33 +73,9 @@ __device__ __forceinline__ double spice_cell(double theta, double so) {
 // P cells of X, widened: one nt load of sizeof(X) * P bytes (16, 8, or the element)
 template <typename X, int P>
 __device__ __forceinline__ void spice_load(const X* __restrict__ p, double (&v)[P]) {
-  X raw[P];
-  if constexpr (sizeof(X) * P == 16) {
-    const spice_f4 r = __builtin_nontemporal_load(reinterpret_cast<const spice_f4*>(p));
-    __builtin_memcpy(raw, &r, 16);
-  } else if constexpr (sizeof(X) * P == 8 && P == 2) {
-    const double r = __builtin_nontemporal_load(reinterpret_cast<const double*>(p));
-    __builtin_memcpy(raw, &r, 8);
-  } else {
-    static_assert(P == 1, "packs are 16 bytes of the widest field");
-    raw[0] = __builtin_nontemporal_load(p);
-  }
+  const Pack<X, P> raw = load_pack<X, P, true>(p);
 #pragma unroll
-  for (int k = 0; k < P; ++k) v[k] = (double)raw[k];  // float -> double: exact
-}
-
-template <int P>
-__device__ __forceinline__ void spice_store(double* __restrict__ p, const double (&v)[P]) {
-  if constexpr (P == 1) {
-    __builtin_nontemporal_store(v[0], p);
-  } else {
-#pragma unroll
-    for (int h = 0; h < P / 2; ++h) {
-      spice_f4 r;
-      __builtin_memcpy(&r, &v[2 * h], 16);
-      __builtin_nontemporal_store(r, reinterpret_cast<spice_f4*>(p) + h);
-    }
-  }
+  for (int k = 0; k < P; ++k) v[k] = (double)raw.v[k];  // float -> double: exact
 }
 
 // Cells [head, head + P * npacks) in packs of P; cells [0, head) and [head + P * npacks, n) -- fewer
@@ -129,10 +104,10 @@ __global__ __launch_bounds__(kSpiceBlock) void k_spice_map(const TT* __restrict_
     for (int u = 0; u < U; ++u) {
       const int64_t i = base + (int64_t)u * kSpiceBlock;
       if (i < npacks) {
-        double r[P];
+        Pack<double, P> r;
 #pragma unroll
-        for (int k = 0; k < P; ++k) r[k] = spice_cell(t[u][k], s[u][k]);
-        spice_store<P>(out + head + P * i, r);
+        for (int k = 0; k < P; ++k) r.v[k] = spice_cell(t[u][k], s[u][k]);
+        store_pack<double, P, true>(out + head + P * i, r);  // (four cells: two accesses of 16)
       }
     }
   }

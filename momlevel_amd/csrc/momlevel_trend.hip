@@ -31,12 +31,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <initializer_list>
-
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_trend.h"
-#include "eos_device.hpp"
-#include "mlx_internal.hpp"
+#include "mlx_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -56,7 +53,9 @@ struct TPack {
 };
 
 // once-read data moves with the `nt` cache policy (the idiom of momlevel_hip.hip's load_pack):
-// one global_load_dword / dwordx2 / dwordx4 per lane
+// one global_load_dword / dwordx2 / dwordx4 per lane.  (Not mlx_pack.hpp's Pack / load_pack /
+// store_pack: on them the two-cell float32 kernels measured slower -- the figures are in that
+// header's comment and in profiles/record_fold_ab.log.)
 template <typename TIn, int V>
 __device__ __forceinline__ TPack<TIn, V> tload(const TIn* __restrict__ p) {
   TPack<TIn, V> r;
@@ -355,9 +354,6 @@ __global__ __launch_bounds__(kTrendBlock) void k_time_apply_model(const TIn* __r
 using detail::fail;
 using detail::hip_status;
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b != 0); }
-
 // Steps per time window of the fit kernels: a function of nt ALONE.  At most 16 windows (their
 // partial sums cost 40 B per cell and window against 8 * window bytes of record), none shorter
 // than 256 steps unless the record is.
@@ -366,34 +362,13 @@ inline int64_t fit_window(int64_t nt) {
   return w < 256 ? 256 : w;
 }
 
-constexpr int64_t kMaxCells = (int64_t)1 << 38;
 constexpr int64_t kMaxSteps = (int64_t)1 << 31;
-
-inline bool record_fits(int64_t nt, int64_t n) {
-  int64_t total;
-  return nt > 0 && n > 0 && nt < kMaxSteps && n <= kMaxCells &&
-         !__builtin_mul_overflow(nt, n, &total) && total <= INT64_MAX / 64;
-}
-
-// cells per lane: the widest pack of `elem`-byte cells (16 bytes at most) that divides every row
-// and keeps every row of every operand 16-byte (or pack-) aligned
-inline int pack_width(int64_t n, size_t elem, std::initializer_list<const void*> ptrs16,
-                      const void* yptr) {
-  for (int v = (int)(16 / elem); v > 1; v /= 2) {
-    if (n % v) continue;
-    bool ok = yptr == nullptr || aligned(yptr, elem * v);
-    for (const void* q : ptrs16) ok = ok && (q == nullptr || aligned(q, 8 * (v > 2 ? 2 : v)));
-    if (ok) return v;
-  }
-  return 1;
-}
 
 inline int check_record(const void* y, int dtype, int64_t nt, int64_t n, bool need_y) {
   if (need_y && !y) return fail(MLX_E_NULL, "y must not be NULL");
-  if (dtype != MLX_DTYPE_F64 && dtype != MLX_DTYPE_F32)
-    return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
-  if (!record_fits(nt, n)) return fail(MLX_E_SHAPE, "need 0 < nt < 2^31, 0 < n <= 2^38, nt*n addressable");
-  if (y && !aligned(y, dtype == MLX_DTYPE_F64 ? 8 : 4)) return fail(MLX_E_ALIGN, "y not element-aligned");
+  if (!is_float_dtype(dtype)) return fail(MLX_E_ENUM, "dtype must be MLX_DTYPE_F64 or MLX_DTYPE_F32");
+  if (!record_fits(nt, n, kMaxSteps)) return fail(MLX_E_SHAPE, "need 0 < nt < 2^31, 0 < n <= 2^38, nt*n addressable");
+  if (y && !aligned(y, dtype_size(dtype))) return fail(MLX_E_ALIGN, "y not element-aligned");
   return 0;
 }
 
@@ -462,7 +437,7 @@ using namespace mlx;
 extern "C" {
 
 size_t mlx_time_fit_workspace_bytes(int64_t nt, int64_t n, int nterms) {
-  if (!record_fits(nt, n) || nterms <= 0 || nterms > MLX_TREND_MAX_TERMS) return 0;
+  if (!record_fits(nt, n, kMaxSteps) || nterms <= 0 || nterms > MLX_TREND_MAX_TERMS) return 0;
   const int64_t windows = ceil_div(nt, fit_window(nt));
   return (size_t)windows * (size_t)nterms * (size_t)n * sizeof(double);
 }
@@ -478,20 +453,13 @@ int mlx_time_linfit(const void* y, int dtype, const double* xt, int64_t nt, int6
     return fail(MLX_E_ALIGN, "xt / slope / intercept not 8-byte aligned");
   if (!aligned(workspace, 16) || workspace_bytes < mlx_time_fit_workspace_bytes(nt, n, kFitTerms))
     return fail(MLX_E_WORKSPACE, "workspace misaligned or smaller than mlx_time_fit_workspace_bytes(nt, n, 5)");
-  if (ceil_div(n, kTrendBlock) > 2147483647LL) return fail(MLX_E_SHAPE, "n too large");
   hipStream_t st = (hipStream_t)stream;
   double* ws = (double*)workspace;
-  int rc;
-  if (dtype == MLX_DTYPE_F64) {
-    const int v = pack_width(n, 8, {ws}, y);
-    rc = v == 2 ? launch_linfit<double, 2>(y, xt, nt, n, ws, st)
-                : launch_linfit<double, 1>(y, xt, nt, n, ws, st);
-  } else {
-    const int v = pack_width(n, 4, {ws}, y);
-    rc = v == 4   ? launch_linfit<float, 4>(y, xt, nt, n, ws, st)
-         : v == 2 ? launch_linfit<float, 2>(y, xt, nt, n, ws, st)
-                  : launch_linfit<float, 1>(y, xt, nt, n, ws, st);
-  }
+  const size_t elem = dtype_size(dtype);
+  const int v = pack_width(n, elem, {{y, elem}, {ws, 8}});
+  const int rc = dispatch_pack(dtype, v, [&](auto t, auto w) {
+    return launch_linfit<typename decltype(t)::type, decltype(w)::value>(y, xt, nt, n, ws, st);
+  });
   if (rc) return rc;
   const int64_t windows = ceil_div(nt, fit_window(nt));
   hipLaunchKernelGGL(k_linfit_finish, dim3((unsigned)ceil_div(n, kTrendBlock)), dim3(kTrendBlock), 0,
@@ -513,17 +481,11 @@ int mlx_time_project(const void* y, int dtype, const double* P, int K, int64_t n
   hipStream_t st = (hipStream_t)stream;
   const int64_t windows = ceil_div(nt, fit_window(nt));
   double* dst = windows == 1 ? coef : (double*)workspace;  // one window: its sums ARE the result
-  int rc;
-  if (dtype == MLX_DTYPE_F64) {
-    const int v = pack_width(n, 8, {dst}, y);
-    rc = v == 2 ? launch_project<double, 2>(y, P, K, nt, n, dst, st)
-                : launch_project<double, 1>(y, P, K, nt, n, dst, st);
-  } else {
-    const int v = pack_width(n, 4, {dst}, y);
-    rc = v == 4   ? launch_project<float, 4>(y, P, K, nt, n, dst, st)
-         : v == 2 ? launch_project<float, 2>(y, P, K, nt, n, dst, st)
-                  : launch_project<float, 1>(y, P, K, nt, n, dst, st);
-  }
+  const size_t elem = dtype_size(dtype);
+  const int v = pack_width(n, elem, {{y, elem}, {dst, 8}});
+  const int rc = dispatch_pack(dtype, v, [&](auto t, auto w) {
+    return launch_project<typename decltype(t)::type, decltype(w)::value>(y, P, K, nt, n, dst, st);
+  });
   if (rc || windows == 1) return rc;
   hipLaunchKernelGGL(k_project_finish, dim3((unsigned)ceil_div(rows, kTrendBlock)), dim3(kTrendBlock),
                      0, st, (const double*)dst, windows, rows, coef);
@@ -544,18 +506,15 @@ int mlx_time_apply(const void* y, int dtype, int mode, const double* xm, const d
   if (!aligned(xm, 8) || !aligned(a, 8) || (b && !aligned(b, 8)) || !aligned(out, 8))
     return fail(MLX_E_ALIGN, "xm / a / b / out not 8-byte aligned");
   if (ceil_div(nt, kApplyWindow) > 65535) return fail(MLX_E_SHAPE, "nt too large for one call: chunk it");
-  if (ceil_div(n, kTrendBlock) > 2147483647LL) return fail(MLX_E_SHAPE, "n too large");
   hipStream_t st = (hipStream_t)stream;
   const void* yy = reads_y ? y : nullptr;
-  if (dtype == MLX_DTYPE_F64 || !reads_y) {
-    const int v = pack_width(n, 8, {out}, yy);
-    return v == 2 ? launch_apply<double, 2>(yy, mode, xm, a, b, K, nt, n, out, st)
-                  : launch_apply<double, 1>(yy, mode, xm, a, b, K, nt, n, out, st);
-  }
-  const int v = pack_width(n, 4, {out}, yy);
-  return v == 4   ? launch_apply<float, 4>(yy, mode, xm, a, b, K, nt, n, out, st)
-         : v == 2 ? launch_apply<float, 2>(yy, mode, xm, a, b, K, nt, n, out, st)
-                  : launch_apply<float, 1>(yy, mode, xm, a, b, K, nt, n, out, st);
+  const int ydtype = reads_y ? dtype : MLX_DTYPE_F64;  // (y is not read: the float64 instantiation)
+  const size_t elem = dtype_size(ydtype);
+  const int v = pack_width(n, elem, {{yy, elem}, {out, 8}});
+  return dispatch_pack(ydtype, v, [&](auto t, auto w) {
+    return launch_apply<typename decltype(t)::type, decltype(w)::value>(yy, mode, xm, a, b, K, nt, n,
+                                                                        out, st);
+  });
 }
 
 }  // extern "C"

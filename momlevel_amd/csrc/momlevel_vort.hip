@@ -33,6 +33,7 @@
 #include "../../include/momlevel_hip.h"
 #include "../../include/momlevel_vort.h"
 #include "mlx_internal.hpp"
+#include "mlx_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -49,8 +50,6 @@ constexpr int64_t kVortMaxCells = (int64_t)1 << 38;
 
 static_assert(kVortLanes == 64 && kVortH % kVortR == 0, "a tile is one wave wide");
 
-typedef float vort_f4 __attribute__((ext_vector_type(4)));
-
 // numpy's promotion of two of {float32, float64}
 template <typename A, typename B>
 struct Promote {
@@ -64,26 +63,18 @@ struct Promote<float, float> {
 // P cells of X in one load of sizeof(X) * P bytes (16, 8, or the element); NT: touched once
 template <typename X, int P, bool NT>
 __device__ __forceinline__ void vort_load(const X* __restrict__ p, X (&v)[P]) {
-  if constexpr (sizeof(X) * P == 16) {
-    const vort_f4* q = reinterpret_cast<const vort_f4*>(p);
-    const vort_f4 r = NT ? __builtin_nontemporal_load(q) : *q;
-    __builtin_memcpy(v, &r, 16);
-  } else if constexpr (sizeof(X) * P == 8 && P == 2) {
-    const double* q = reinterpret_cast<const double*>(p);
-    const double r = NT ? __builtin_nontemporal_load(q) : *q;
-    __builtin_memcpy(v, &r, 8);
-  } else {
-    static_assert(P == 1, "packs are 16 bytes of the arithmetic dtype");
-    v[0] = NT ? __builtin_nontemporal_load(p) : *p;
-  }
+  const Pack<X, P> r = load_pack<X, P, NT>(p);
+#pragma unroll
+  for (int k = 0; k < P; ++k) v[k] = r.v[k];
 }
 
 template <typename X, int P>
 __device__ __forceinline__ void vort_store(X* __restrict__ p, const X (&v)[P]) {
   static_assert(sizeof(X) * P == 16, "a pack of the result is 16 bytes");
-  vort_f4 r;
-  __builtin_memcpy(&r, v, 16);
-  __builtin_nontemporal_store(r, reinterpret_cast<vort_f4*>(p));
+  Pack<X, P> r;
+#pragma unroll
+  for (int k = 0; k < P; ++k) r.v[k] = v[k];
+  store_pack<X, P, true>(p, r);
 }
 
 __device__ __forceinline__ float vort_abs(float x) { return __builtin_fabsf(x); }

@@ -8,8 +8,9 @@ kernel with the same time-strided access pattern.
 Per dtype (float64, float32) the cases run ALTERNATING, round after round, in one process; each
 case is timed with device events around enough calls to fill ``--window-ms``; the median over the
 rounds is reported with the spread (min .. max) beside it.  Bytes are what the algorithm has to
-move: fit / projection read the record once (8 or 4 B per cell-step), the apply pass reads it and
-writes float64 (16 or 12 B).  ``frac_of_8TBs`` is bytes / time over the 8 TB/s peak; ``vs_probe``
+move: fit / projection read the record once (8 or 4 B per cell-step), the apply pass (the straight
+line removed, and the residual of the 6-term seasonal model) reads it and writes float64 (16 or
+12 B). ``frac_of_8TBs`` is bytes / time over the 8 TB/s peak; ``vs_probe``
 the probe's time over the kernel's.  These are call times (workspace allocation from torch's
 cache and the small finishing kernel included); kernel times come from a separate
 ``rocprofv3 --kernel-trace --stats`` run of this script, condensed with ``--stats-dir``.
@@ -93,6 +94,7 @@ def main():
                              scale=2.0, mask3d=mask).reshape(nt, ny, nx)
         flat = y.reshape(-1)
         slope, icpt = core.time_linfit(y, xtd, s, xmean)
+        coef = core.time_project(y, Pd)
         gwm_out = torch.empty((nt // 12, ny, nx), dtype=torch.float64, device="cuda")
         cases = [
             ("k_time_linfit", item, lambda: core.time_linfit(y, xtd, s, xmean), "probe_read"),
@@ -100,6 +102,8 @@ def main():
             ("probe_read", item, lambda: core.stream_probe_mix(flat, write=False), None),
             ("k_time_apply remove", item + 8,
              lambda: core.time_apply(y, "remove", xd, slope, icpt, out=out), "probe_read_write"),
+            ("k_time_apply model_resid<6>", item + 8,
+             lambda: core.time_apply(y, "model_resid", Md, coef, out=out), "probe_read_write"),
             ("probe_read_write", item + 8,
              lambda: core.stream_probe_mix(flat, out=out.reshape(-1), write=True), None),
         ]
@@ -137,7 +141,7 @@ def main():
             print(json.dumps({"baseline": "np.polyfit on the host, 1/64 slab (ocean columns only)",
                               "columns": int(ocean.shape[1]), "wall_s": round(dt_s, 3),
                               "whole_record_s_extrapolated": round(dt_s * 64, 1)}), flush=True)
-        del y, flat, slope, icpt, gwm_out, cases
+        del y, flat, slope, icpt, coef, gwm_out, cases
         torch.cuda.empty_cache()
     return 0
 

@@ -13,6 +13,9 @@ process:
   bytes (two fields in, one out: 24 B per cell at float64, 12 at float32; the 2-D metrics are read
   from cache), the rate they imply and the ratio to the probe.
 
+After the two dtypes, one case per mixed-dtype instantiation of the packed kernels (fields of one
+dtype and metrics of the other; zeta, coriolis and n2 in every combination that is not uniform).
+
 The last lines state the acceptance condition per float64 pass: it takes no longer than the probe's
 time x the algorithmic byte ratio of the tiling, (24 + 8 / H) / 24 -- the halo row, nothing else --
 plus the spread (max - min) of the probe's own rounds.
@@ -170,6 +173,27 @@ def main():
                             "probe_spread_ms": round(pmax - pmin, 4), "limit_ms": round(limit, 4),
                             "met": bool(ms <= limit)})
         del u, v, n2, f, dx, dy, area, out, zeta
+    # operands of both dtypes in one call (the result is float64): the packed kernels' other
+    # instantiations, one case each
+    kinds = {"float64": torch.float64, "float32": torch.float32}
+    out = torch.empty(shape, dtype=torch.float64, device="cuda")
+    zeta64 = core.rel_vort(u64, v64, *m64)
+    for tf, tm in (("float64", "float32"), ("float32", "float64")):
+        u, v = u64.to(kinds[tf]), v64.to(kinds[tf])
+        dx, dy, area = (m.to(kinds[tm]) for m in m64)
+        measure(f"rel_vort, {tf} fields, {tm} metrics",
+                lambda: core.rel_vort(u, v, dx, dy, area, out=out), a, n * (2 * u.element_size() + 8))
+    for tz in kinds:
+        for tc in kinds:
+            for tn in kinds:
+                if tz == tc == tn:
+                    continue
+                zeta, f, n2 = zeta64.to(kinds[tz]), f64.to(kinds[tc]), n264.to(kinds[tn])
+                for interp in (True, False):
+                    measure(f"potential_vorticity ({'interp' if interp else 'no interp'}, m), zeta {tz}, "
+                            f"coriolis {tc}, n2 {tn}",
+                            lambda: core.potential_vorticity(zeta, f, n2, interp=interp, out=out), a,
+                            n * (zeta.element_size() + n2.element_size() + 8))
     for row in met:
         print(json.dumps(row), flush=True)
     return 0

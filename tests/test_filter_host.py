@@ -369,7 +369,7 @@ def test_features_has_the_row_and_a_sha_of_its_own():
     from momlevel_amd.csrc import build
 
     assert build.FEATURES["filter"] == ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp",
-                                        "include/momlevel_filter.h"]
+                                        "mlx_record.hpp", "include/momlevel_filter.h"]
     assert len(build.filter_source_sha()) == 16
     assert build.filter_source_sha() == build.feature_source_sha("filter")
     assert build.filter_source_sha() not in (build.source_sha(), build.clim_source_sha(),

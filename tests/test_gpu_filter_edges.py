@@ -5,7 +5,8 @@ inside a time tile.
 The cell counts are test_gpu_clim_edges.py's (float64: 511, 512, 513, 1026, 1030; float32: 513,
 1023, 1024, 1026, 2052 -- one, two and four cells a lane over up to four blocks of 256 lanes, the
 last one ragged), and a record that fills a pack is also placed 1 and 2 elements into a flat buffer:
-the narrower kernels must give the aligned result bit for bit.
+the narrower kernels must give the aligned result bit for bit.  So must a float64 result written 8
+bytes off a 16-byte boundary; test_windows_on_every_edge also runs on 8 float32 cells for that.
 
 The record has nt = min(96, about 2 1/2 time tiles) steps, but at least W + 3: tile and window edges
 come from the library's own queries (core.filter_tile, core.filter_window_edges).  Windows: 1, 2, 3,
@@ -107,7 +108,7 @@ def _check(y, dtype, window, lead, label, w, mc, norm, placements):
     return want64
 
 
-@pytest.mark.parametrize("dtype, n", CELLS, ids=CELL_IDS)
+@pytest.mark.parametrize("dtype, n", CELLS + [(np.float32, 8)], ids=CELL_IDS + ["float32-8"])
 def test_windows_on_every_edge(dtype, n):
     tile = core.filter_tile()
     rng = np.random.default_rng(n)
@@ -128,6 +129,14 @@ def test_windows_on_every_edge(dtype, n):
         full = core.time_filter(placements[0][1], np.ones(window), lead, 1, True,
                                 out_dtype=torch.float64).cpu().numpy()
         assert_bit_equal(full, fn.time_filter(y, np.ones(window), lead, 1, True), "float64 out")
+        # the same into a result 8 bytes off a 16-byte boundary: narrower packs, the aligned bits
+        buf = torch.full((nt * n + 2,), -7.0, dtype=torch.float64, device=DEV)
+        view = buf[1:1 + nt * n].view(nt, n)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() == buf.data_ptr() + 8
+        assert core.time_filter(placements[0][1], np.ones(window), lead, 1, True, out=view,
+                                out_dtype=torch.float64) is view
+        assert_bit_equal(view.cpu().numpy(), full, "float64 out, 8 bytes off")
+        assert buf[0].item() == -7.0 and buf[-1].item() == -7.0, "wrote outside the result"
         low = core.time_filter(placements[0][1], np.ones(window), lead, 1, False,
                                out_dtype=torch.float32).cpu().numpy()
         assert_bit_equal(low, fn.time_filter(y, np.ones(window), lead, 1, False).astype(np.float32),

@@ -258,5 +258,15 @@ def test_exceed_count(dtype):
         assert np.array_equal(got.cpu().numpy(), want), f"off={off}"
     got32 = core.time_exceed_count(_place(y), torch.from_numpy(thr.astype(np.float32)).to(DEV))
     assert np.array_equal(got32.cpu().numpy(), qn.exceed_count(y, thr.astype(np.float32)))
+    # 8 cells fill a pack; a threshold 8 bytes off a 16-byte boundary takes the one-cell kernel: its
+    # counts are the aligned ones
+    y8, thr8 = np.ascontiguousarray(y[:, :8]), np.ascontiguousarray(thr[:, :8])
+    buf = torch.zeros(8 + 2, dtype=torch.float64, device=DEV)
+    buf[1:9] = torch.from_numpy(thr8[0]).to(DEV)
+    shifted = buf[1:9].view(1, 8)
+    assert buf.data_ptr() % 16 == 0 and shifted.data_ptr() == buf.data_ptr() + 8
+    aligned = core.time_exceed_count(_place(y8), torch.from_numpy(thr8).to(DEV)).cpu().numpy()
+    assert np.array_equal(aligned, qn.exceed_count(y8, thr8)) and aligned.any()
+    assert core.time_exceed_count(_place(y8), shifted).cpu().numpy().tobytes() == aligned.tobytes()
     with pytest.raises(ValueError):
         core.time_exceed_count(_place(y), torch.zeros((2, n), dtype=torch.float64, device=DEV))

@@ -416,7 +416,7 @@ def test_features_has_the_row_and_a_sha_of_its_own():
     from momlevel_amd.csrc import build
 
     assert build.FEATURES["quantile"] == ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp",
-                                          "include/momlevel_quantile.h"]
+                                          "mlx_record.hpp", "include/momlevel_quantile.h"]
     assert len(build.quantile_source_sha()) == 16
     assert build.quantile_source_sha() == build.feature_source_sha("quantile")
     assert build.quantile_source_sha() not in (build.source_sha(), build.clim_source_sha(),
