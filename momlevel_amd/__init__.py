@@ -8,7 +8,7 @@ detrend and deseason fits of ``trend``, and the grouped time statistics
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
 include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
-include/momlevel_quantile.h).
+include/momlevel_quantile.h, include/momlevel_column.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -45,6 +45,12 @@ lives: ``time_quantile`` / ``time_median`` (the values of xarray's ``.quantile(q
 over the whole record, per calendar month or per year) by radix select in registers, and
 ``exceedance_count``, the steps above a number, a per-cell field or those quantiles
 (include/momlevel_quantile.h).
+
+``derived.calc_mld``, ``derived.calc_isosurface_depth`` and ``derived.calc_isopycnal_depth`` (EXTENSIONS
+too) answer the vertical questions of a ``(..., z, yh, xh)`` field where it lives: the mixed layer
+depth by a density or temperature threshold, the depth of the 20 degC isotherm, the depth of
+sigma0 = 27 -- one search down every column that stops reading at the crossing, the potential
+density evaluated inside it and never written out (include/momlevel_column.h).
 
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 

@@ -52,6 +52,10 @@ LAYER_MAX = 8
 FILTER_NORMALISE = 1
 # ---- constants mirrored from include/momlevel_quantile.h ----------------------------
 QUANTILE_MAX_Q = 8
+# ---- constants mirrored from include/momlevel_column.h -----------------------------
+COLUMN_MAX_TARGETS = 8
+COLUMN_RISE, COLUMN_FALL, COLUMN_DEPART = 0, 1, 2
+COLUMN_MISS_NAN, COLUMN_MISS_FLOOR = 0, 1
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -235,6 +239,16 @@ QUANTILE_SIGNATURES = {
 }
 
 
+# The column search (include/momlevel_column.h): bound by load_column() on first use, for the same
+# reason.
+COLUMN_SIGNATURES = {
+    "mlx_column_block_cells": (_i64, [_int, _int, _int, _int]),
+    "mlx_column_record_rows": (_int, [_i64]),
+    "mlx_column_crossing": (_int, [_vp, _int, _vp, _int, _int, _dbl, _i64, _i64, _i64, _vp, _i64,
+                                   _int, _int, _int, _vp, _int, _vp, _vp, _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -312,12 +326,13 @@ _GROUPS = {
     "filter": (FILTER_SIGNATURES, "the time-filter kernel"),
     "path": (PATH_SIGNATURES, "the path queries of the EOS maps"),
     "quantile": (QUANTILE_SIGNATURES, "the quantile kernels"),
+    "column": (COLUMN_SIGNATURES, "the column-search kernel"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
-_layer_bound = _filter_bound = _path_bound = _quantile_bound = False
+_layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = False
 
 
 def _load_group(group):
@@ -369,6 +384,10 @@ def load_path():
 
 def load_quantile():
     return _load_group("quantile")
+
+
+def load_column():
+    return _load_group("column")
 
 
 def last_error():

@@ -1463,6 +1463,82 @@ def layer_integral(x, z_i, depth, tops, bottoms, surface=None, scale=1.0, out=No
 
 
 # ---------------------------------------------------------------------------------------
+# the column search (include/momlevel_column.h; csrc/momlevel_column.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+COLUMN_MAX_TARGETS = _lib.COLUMN_MAX_TARGETS  # targets per launch of column_crossing
+COLUMN_MODES = {"rise": _lib.COLUMN_RISE, "fall": _lib.COLUMN_FALL, "depart": _lib.COLUMN_DEPART}
+COLUMN_MISS = {"nan": _lib.COLUMN_MISS_NAN, "floor": _lib.COLUMN_MISS_FLOOR}
+
+
+def column_block_cells(a_dtype=torch.float64, b_dtype=None, generic=False):
+    """Cells of the plane one block of column_crossing covers (mlx_column_block_cells) for a field
+    of ``a_dtype`` and, SIGMA source, a salinity of ``b_dtype``: 256 packs of 16 bytes of the wider
+    field, or 256 single cells on the ``generic`` path."""
+    return int(_lib.load_column().mlx_column_block_cells(
+        _query_dtype(a_dtype), int(b_dtype is not None),
+        _query_dtype(b_dtype) if b_dtype is not None else 0, int(bool(generic))))
+
+
+def column_record_rows(nrec):
+    """Block rows along the records of a column_crossing call over ``nrec`` records
+    (mlx_column_record_rows): ``min(nrec, cap)``; past the cap a row goes on to further records.
+    0 for nrec <= 0."""
+    return int(_lib.load_column().mlx_column_record_rows(int(nrec)))
+
+
+def column_crossing(a, z, targets, b=None, kref=0, mode="rise", relative=False, miss="nan",
+                    floor=None, eos="wright", p_ref=101325.0, out=None):
+    """Depth of the first crossing along z (mlx_column_crossing), as tests/column_numpy.py.
+
+    ``a`` (nrec, nz, plane) contiguous float32 / float64 device tensor: the field (FIELD source),
+    or theta when ``b``, the salinity of the same shape (its own dtype), is given -- the column
+    value is then the float64 density of the widened pair at the scalar pressure ``p_ref`` (SIGMA
+    source).  ``z`` the nz level depths; ``targets`` a host sequence; ``kref`` the reference
+    level; ``mode`` "rise" | "fall" | "depart"; ``relative``: targets are offsets from the value at
+    ``kref``; ``miss`` "nan" | "floor": what a column without a crossing gets (``floor`` (plane)
+    when given, else the depth of its deepest level with a value).  Returns (nrec, ntargets,
+    plane) float64 (``out`` when given).  More than COLUMN_MAX_TARGETS targets run as several
+    launches over groups of targets; every target gets the bits it would get alone."""
+    require_device()
+    lib = _lib.load_column()
+    adt = _float_code(a, "a", 3)
+    nrec, nz, plane = (int(n) for n in a.shape)
+    dev = a.device
+    bdt = 0
+    if b is not None:
+        bdt = _float_code(b, "b", 3)
+        if tuple(b.shape) != tuple(a.shape) or b.device != dev:
+            raise ValueError("a and b must agree in shape and device")
+    try:
+        mode_id, miss_id, eos_id = COLUMN_MODES[mode], COLUMN_MISS[miss], EOS_IDS[str(eos).lower()]
+    except KeyError as exc:
+        raise ValueError(f"unknown mode / miss / eos {exc}") from None
+    targets = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1)
+    nt = int(targets.size)
+    if nt < 1:
+        raise ValueError("targets must hold one value at least")
+    z = _f64(z, dev).reshape(-1)
+    if z.numel() != nz:
+        raise ValueError(f"z must have nz = {nz} entries")
+    if floor is not None:
+        floor = _f64(floor, dev).reshape(-1)
+        if floor.numel() != plane:
+            raise ValueError(f"floor must hold {plane} cells")
+    out = _out_like(out, (nrec, nt, plane), torch.float64, dev, "float64")
+    groups = layer_groups(nt, COLUMN_MAX_TARGETS)
+    for start, count in groups:
+        part = out if len(groups) == 1 else torch.empty((nrec, count, plane), dtype=torch.float64,
+                                                        device=dev)
+        t = targets[start:start + count].copy()
+        _call(lib, "mlx_column_crossing", dev, _ptr(a), adt, _ptr(b), bdt, eos_id, float(p_ref),
+              nrec, nz, plane, _ptr(z), int(kref), mode_id, int(bool(relative)), miss_id,
+              t.ctypes.data, count, _ptr(floor), _ptr(part))
+        if part is not out:
+            out[:, start:start + count] = part
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # the time filter (include/momlevel_filter.h; csrc/momlevel_filter.hip).  EXTENSION.
 # ---------------------------------------------------------------------------------------
 def filter_tile():

@@ -35,6 +35,7 @@ FEATURES = {
                "include/momlevel_filter.h"],
     "quantile": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
                  "include/momlevel_quantile.h"],
+    "column": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_column.h"],
 }
 
 
@@ -147,6 +148,11 @@ def filter_source_sha():
 def quantile_source_sha():
     """the quantile kernels' own guard: csrc/momlevel_quantile.hip (+ what it includes, + flags)"""
     return feature_source_sha("quantile")
+
+
+def column_source_sha():
+    """the column-search kernel's own guard: csrc/momlevel_column.hip (+ what it includes, + flags)"""
+    return feature_source_sha("column")
 
 
 def hipcc():

@@ -18,7 +18,7 @@ import torch
 
 from . import core, engine, hostio, spice, util
 from .adapters import accepts_xarray
-from .labeled import DataArray, check_field_dtype, is_lazy
+from .labeled import DataArray, as_plain, check_field_dtype, is_lazy
 from .steric import OHC_CP
 
 __all__ = [
@@ -28,8 +28,11 @@ __all__ = [
     "calc_coriolis",
     "calc_dz",
     "calc_heat_content",
+    "calc_isopycnal_depth",
+    "calc_isosurface_depth",
     "calc_layer_integral",
     "calc_masso",
+    "calc_mld",
     "calc_n2",
     "calc_pdens",
     "calc_pv",
@@ -729,6 +732,55 @@ def calc_rossby_rd(wave_speed, coriolis):
 
 
 # ---------------------------------------------------------------------------------------
+# (..., z, y, x) fields seen as (records, z, plane): shared by the depth-layer sums and the column
+# search
+# ---------------------------------------------------------------------------------------
+def _z_plane(field, zcoord, zi, depth=None):
+    """(dims, shape) of the two horizontal dims behind ``zcoord``; with ``depth``: its plane"""
+    hdims, hshape = tuple(field.dims[zi + 1:]), tuple(int(n) for n in field.shape[zi + 1:])
+    if depth is not None:
+        if len(hdims) != 2 or hshape != tuple(int(n) for n in depth.shape):
+            raise ValueError(f"the field's dims behind {zcoord!r} are {hdims}{hshape}: expected "
+                             f"depth's plane {tuple(depth.shape)}")
+    elif len(hdims) != 2:
+        raise ValueError(f"the field's dims behind {zcoord!r} are {hdims}{hshape}: two horizontal "
+                         "dims are expected")
+    return hdims, hshape
+
+
+def _over_z_records(fields, zi, nout, dev, kernel):
+    """``kernel(tensors)`` on the (records, nz, plane) device views of ``fields`` -- labelled
+    float32 / float64 arrays of one shape ``lead + (nz, y, x)``, each kept in its own dtype (other
+    dtypes compute as float64) -- where it returns ``(records, nout, plane)``  ->  the raw result of
+    shape ``lead + (nout, y, x)``: a device tensor when a field lives on the device, else a host
+    array.  A large host or lazy field goes up in groups of whole leading rows and is never
+    materialised whole: a record's result depends on that record alone, so the grouping cannot show."""
+    first = fields[0]
+    shape_in = tuple(int(n) for n in first.shape)
+    lead, nz, hshape = shape_in[:zi], shape_in[zi], shape_in[zi + 1:]
+    nrec = int(np.prod(lead, dtype=np.int64))
+    plane = int(np.prod(hshape, dtype=np.int64))
+    shape = lead + (nout,) + hshape
+    on_device = any(f.is_device for f in fields)
+    dts = [torch.float32 if str(f.dtype) == "float32" else torch.float64 for f in fields]
+
+    def run(tensors, n):
+        return kernel([x.to(dt).reshape(n, nz, plane) for x, dt in zip(tensors, dts)])
+
+    if not on_device and len(lead) >= 1 and hostio.wants_pipeline(lead[0], nrec * nz * plane):
+        inner = nrec // lead[0]
+        sources = [f.data if f.is_lazy else f.values for f in fields]
+        return hostio.pipeline_rows(
+            hostio.row_bounds(lead[0], inner * nz * plane), dev, hostio.leading_slices(sources),
+            lambda tensors, i0, i1: run(tensors, (i1 - i0) * inner),
+            np.empty(shape, dtype=np.float64))
+    xs = [f.data if f.is_device else engine.to_device(f.values, dev, dt)
+          for f, dt in zip(fields, dts)]
+    out = run([x.contiguous() for x in xs], nrec).reshape(shape)
+    return out if on_device else hostio.to_host(out)
+
+
+# ---------------------------------------------------------------------------------------
 # depth-layer sums (EXTENSION; csrc/momlevel_layer.hip)
 # ---------------------------------------------------------------------------------------
 def layer_bounds(layers):
@@ -825,10 +877,7 @@ def calc_layer_integral(field, interfaces, depth, layers, zcoord="z_l", scale=1.
     if depth.ndim != 2:
         raise ValueError(f"depth has dims {depth.dims}: a 2-D (y, x) field is expected")
     zi, nrec, nz, plane = _z_layout(field, zcoord)
-    hdims, hshape = tuple(field.dims[zi + 1:]), tuple(int(n) for n in field.shape[zi + 1:])
-    if len(hdims) != 2 or hshape != tuple(int(n) for n in depth.shape):
-        raise ValueError(f"the field's dims behind {zcoord!r} are {hdims}{hshape}: expected depth's "
-                         f"plane {tuple(depth.shape)}")
+    hdims, hshape = _z_plane(field, zcoord, zi, depth)
     z_i = np.asarray(interfaces.values if isinstance(interfaces, DataArray) else interfaces,
                      dtype=np.float64).reshape(-1)
     if z_i.size != nz + 1:
@@ -850,32 +899,13 @@ def calc_layer_integral(field, interfaces, depth, layers, zcoord="z_l", scale=1.
             raise ValueError(f"wet {tuple(wet.shape)} does not cover the plane {hshape}")
 
     dev = engine.device_of(field.data, depth.data)
-    on_device = field.is_device
-    tdt = torch.float32 if str(field.dtype) == "float32" else torch.float64
     z_d = engine.to_device(z_i, dev, torch.float64)
     depth_d = engine.to_device(depth.data, dev, torch.float64).contiguous().reshape(-1)
     wet_d = None if wet is None else engine.to_device(wet, dev, torch.float64).contiguous().reshape(-1)
     nl = len(tops)
-    lead = tuple(int(n) for n in field.shape[:zi])
-    shape = lead + (nl,) + hshape
-
-    def integral(x, n):
-        return core.layer_integral(x.to(tdt).reshape(n, nz, plane), z_d, depth_d, tops, bottoms,
-                                   surface=wet_d, scale=scale)
-
-    if not on_device and len(lead) >= 1 and hostio.wants_pipeline(lead[0], nrec * nz * plane):
-        # a record's layers depend on that record alone: the grouping cannot show in the result
-        inner = nrec // lead[0]
-        source = field.data if field.is_lazy else field.values
-        out = hostio.pipeline_rows(
-            hostio.row_bounds(lead[0], inner * nz * plane), dev, hostio.leading_slices([source]),
-            lambda tensors, i0, i1: integral(tensors[0], (i1 - i0) * inner),
-            np.empty(shape, dtype=np.float64))
-    else:
-        x = field.data if on_device else engine.to_device(field.values, dev, tdt)
-        out = integral(x.contiguous(), nrec).reshape(shape)
-        if not on_device:
-            out = hostio.to_host(out)
+    out = _over_z_records(
+        [field], zi, nl, dev,
+        lambda xs: core.layer_integral(xs[0], z_d, depth_d, tops, bottoms, surface=wet_d, scale=scale))
     coords = {k: c for k, c in field.coords.items() if zcoord not in c.dims}
     coords.update(_layer_coords(tops, bottoms))
     return DataArray(out, tuple(field.dims[:zi]) + ("layer",) + hdims, coords, None, field.name)
@@ -903,3 +933,192 @@ def calc_heat_content(thetao, interfaces, depth, layers=None, rhozero=1035.0, cp
         "comment": f"rhozero={rhozero} kg m-3 * cp={cp} J kg-1 K-1 * sum_z(thetao*dz)",
     })
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# the column search: mixed layer, isotherm and isopycnal depths (EXTENSION; csrc/momlevel_column.hip)
+# ---------------------------------------------------------------------------------------
+def _first_record_level_means(field, zi, dev):
+    """NaN-skipping mean of every level of the FIRST record of ``field``, on the host: one small
+    device reduction (core.area_mean with unit areas over the (nz, plane) record)"""
+    shape = tuple(int(n) for n in field.shape)
+    nz, plane = shape[zi], int(np.prod(shape[zi + 1:], dtype=np.int64))
+    dt = torch.float32 if str(field.dtype) == "float32" else torch.float64
+    if field.is_device:
+        rec = field.data.reshape((-1, nz, plane))[0].to(dt).contiguous()
+    else:
+        src = field.data if field.is_lazy else field.values
+        rec = as_plain(src[(slice(0, 1),) * zi]) if zi else field.values  # one record is read
+        rec = engine.to_device(np.ascontiguousarray(rec).reshape(nz, plane), dev, dt)
+    mean, _ = core.area_mean(rec, torch.ones(plane, dtype=torch.float64, device=dev))
+    return mean.reshape(-1).cpu().numpy()
+
+
+def _column_depth(fields, values, zcoord, kref, mode, relative, miss, deptho, value_dim, attrs,
+                  value_attrs=None, eos="wright", p_ref=0.0):
+    """core.column_crossing on labelled ``fields`` ([field], or [thetao, so]: SIGMA source) ->
+    a labelled float64 depth of dims ``lead + (value_dim, y, x)`` (``values`` a sequence) or
+    ``lead + (y, x)`` (a scalar).  ``kref``: a level index, or a function of the level depths;
+    ``mode``: "rise" | "fall" | "depart" | "auto" (rise or fall, from the first record)."""
+    first = fields[0]
+    for f, what in zip(fields, ("field", "so") if len(fields) == 1 else ("thetao", "so")):
+        if not isinstance(f, DataArray):
+            raise TypeError(f"{what} must be a DataArray (a Dataset is not accepted)")
+        float_name(f, what, allow_other=True)
+        if tuple(f.dims) != tuple(first.dims) or tuple(f.shape) != tuple(first.shape):
+            raise ValueError(f"thetao {first.dims}{tuple(first.shape)} and so {f.dims}"
+                             f"{tuple(f.shape)} must agree in dims and shape")
+    zi, nrec, nz, plane = _z_layout(first, zcoord)
+    if deptho is not None and not isinstance(deptho, DataArray):
+        deptho = DataArray(deptho)
+    if deptho is not None and deptho.ndim != 2:
+        raise ValueError(f"deptho has dims {deptho.dims}: a 2-D (y, x) field is expected")
+    hdims, _ = _z_plane(first, zcoord, zi, deptho)
+    z = np.asarray(_level_values(first, zcoord), dtype=np.float64).reshape(-1)
+    if z.size != nz or np.isnan(z).any() or not np.all(np.diff(z) > 0):
+        raise ValueError(f"the levels of {zcoord!r} must increase strictly (depth, positive down)")
+    scalar = np.ndim(values) == 0
+    vals = np.atleast_1d(np.asarray(values, dtype=np.float64)).reshape(-1)
+    if vals.size < 1 or np.isnan(vals).any():
+        raise ValueError("values must hold one number at least and no NaN")
+    if relative and not np.all(vals > 0):
+        raise ValueError("a threshold relative to the reference level must be > 0")
+    kref = int(kref(z)) if callable(kref) else int(kref)
+
+    dev = engine.device_of(*[f.data for f in fields], *([] if deptho is None else [deptho.data]))
+    if mode == "auto":
+        m = _first_record_level_means(first, zi, dev)
+        m = m[~np.isnan(m)]
+        if m.size < 2 or m[-1] == m[0]:
+            raise ValueError("direction='auto' cannot tell: the first record's level means do not "
+                             "differ between its shallowest and deepest level; pass a direction")
+        mode = "rise" if m[-1] > m[0] else "fall"
+    z_d = engine.to_device(z, dev, torch.float64)
+    floor_d = None if deptho is None else (
+        engine.to_device(deptho.data, dev, torch.float64).contiguous().reshape(-1))
+    out = _over_z_records(
+        fields, zi, vals.size, dev,
+        lambda xs: core.column_crossing(xs[0], z_d, vals, b=xs[1] if len(xs) > 1 else None,
+                                        kref=kref, mode=mode, relative=relative, miss=miss,
+                                        floor=floor_d, eos=eos, p_ref=p_ref))
+    lead_dims = tuple(first.dims[:zi])
+    coords = {k: c for k, c in first.coords.items() if zcoord not in c.dims}
+    if scalar:
+        out = out.reshape(tuple(out.shape[:zi]) + tuple(out.shape[zi + 1:]))
+        return DataArray(out, lead_dims + hdims, coords, dict(attrs), None)
+    coords[value_dim] = DataArray(vals.copy(), (value_dim,), None, dict(value_attrs or {}), value_dim)
+    return DataArray(out, lead_dims + (value_dim,) + hdims, coords, dict(attrs), None)
+
+
+_DIRECTIONS = {"increasing": "rise", "decreasing": "fall", "auto": "auto"}
+
+
+@accepts_xarray
+def calc_isosurface_depth(field, values, zcoord="z_l", direction="auto", missing="nan",
+                          deptho=None):
+    """EXTENSION (not in momlevel): the depth at which ``field`` (``(..., z, y, x)``) first reaches
+    each of ``values`` going down from the surface, linearly interpolated between the two levels
+    around the crossing -- the specification is the numpy restatement tests/column_numpy.py.
+
+    ``direction``: "increasing" (the field grows with depth: the first level with
+    ``field >= value``), "decreasing" (``field <= value``: the 20 degC isotherm of a temperature
+    field) or "auto".  "auto" decides ONCE, from the first record alone: the NaN-skipping
+    horizontal mean of every level is taken on the device (one small reduction, nothing of the
+    field is downloaded) and the deepest level's mean is compared with the shallowest's --
+    greater: "increasing", smaller: "decreasing", equal or a single level: ``ValueError``.
+    ``missing``: what a column that never reaches a value gets -- "nan", or "floor": ``deptho``
+    where given, else the depth of the column's deepest level with a value.  A value the surface
+    level has already reached (an outcrop) and land give NaN.
+
+    A list of ``values`` gives dims ``lead + ("value", y, x)`` with the coordinate ``value``; a
+    scalar drops the dim.  float64 metres; device input gives device output."""
+    if direction not in _DIRECTIONS:
+        raise ValueError(f"direction must be 'increasing', 'decreasing' or 'auto', got {direction!r}")
+    if missing not in core.COLUMN_MISS:
+        raise ValueError(f"missing must be 'nan' or 'floor', got {missing!r}")
+    attrs = {"long_name": "Depth of the isosurface", "units": "m", "positive": "down"}
+    of = field.attrs.get("standard_name") if isinstance(field, DataArray) else None
+    if of:
+        attrs["standard_name"] = f"depth_of_isosurface_of_{of}"
+    value_attrs = {k: field.attrs[k] for k in ("standard_name", "units")
+                   if isinstance(field, DataArray) and k in field.attrs}
+    return _column_depth([field], values, zcoord, 0, _DIRECTIONS[direction], False, missing,
+                         deptho, "value", attrs, value_attrs)
+
+
+@accepts_xarray
+def calc_isopycnal_depth(thetao, so, values, level=0.0, patm=101325, eos="Wright", zcoord="z_l"):
+    """EXTENSION (not in momlevel): the depth at which the potential density referenced to
+    ``level`` (p = level*1e4 + patm, as calc_pdens) first reaches each of ``values`` (kg m-3, e.g.
+    1027.0 for sigma0 = 27) going down from the surface; NaN where it never does, where the surface
+    is denser already, and on land.  The density is evaluated inside the search, in float64 on the
+    widened values whatever the dtype of ``thetao`` and ``so`` (include/momlevel_column.h says
+    why): for float64 fields the bits of calc_pdens, which is never materialised.  Dims
+    ``lead + ("rhopot", y, x)`` for a list of values; a scalar drops the dim."""
+    assert 0.0 <= level <= 7500.0, "specified level must be between 0 and 7500 m"
+    attrs = {
+        "standard_name": "depth_of_isosurface_of_sea_water_potential_density",
+        "long_name": f"Depth of the isopycnal (potential density referenced to {level} m)",
+        "comment": f"calculated with the {eos} equation of state",
+        "units": "m",
+        "positive": "down",
+    }
+    value_attrs = {"standard_name": "sea_water_potential_density", "units": "kg m-3"}
+    return _column_depth([thetao, so], values, zcoord, 0, "rise", False, "nan", None, "rhopot",
+                         attrs, value_attrs, eos=_eos_name(eos), p_ref=(level * 1.0e4) + patm)
+
+
+def _eos_name(eos):
+    name = str(eos).lower()
+    if name not in core.EOS_IDS:
+        raise ValueError(f"unknown equation of state {eos!r}")
+    return name
+
+
+MLD_THRESHOLDS = {"density": 0.03, "temperature": 0.2}
+
+
+@accepts_xarray
+def calc_mld(thetao, so=None, criterion="density", threshold=None, ref_depth=10.0, level=0.0,
+             patm=101325, eos="Wright", zcoord="z_l", deptho=None):
+    """EXTENSION (not in momlevel): mixed layer depth by a threshold criterion (de Boyer Montegut
+    et al. 2004).
+
+    ``criterion="density"``: the depth at which the potential density (referenced to ``level``, as
+    calc_pdens; evaluated in float64 inside the search) exceeds its value at the reference level by
+    ``threshold`` (default 0.03 kg m-3); needs ``so``.  ``criterion="temperature"``: the depth at
+    which ``thetao`` departs from its value at the reference level by ``threshold`` (default
+    0.2 degC) either way.  The reference level is the level nearest ``ref_depth`` (ties to the
+    shallower), found on the host from the ``zcoord`` values, which must increase strictly.  The
+    depth is linearly interpolated between the two levels around the crossing.  A column in which
+    the threshold is never reached is mixed to the bottom: ``deptho`` where given, else the depth
+    of its deepest level with a value.  Land is NaN.  float64 metres, dims ``lead + (y, x)``; a
+    list of thresholds gives ``lead + ("threshold", y, x)``.  Device input gives device output."""
+    if criterion not in MLD_THRESHOLDS:
+        raise ValueError(f"criterion must be 'density' or 'temperature', got {criterion!r}")
+    if criterion == "density" and so is None:
+        raise ValueError("criterion='density' needs so (the salinity)")
+    assert 0.0 <= level <= 7500.0, "specified level must be between 0 and 7500 m"
+    if threshold is None:
+        threshold = MLD_THRESHOLDS[criterion]
+    if not np.all(np.asarray(threshold, dtype=np.float64) > 0):
+        raise ValueError("threshold must be > 0")
+    ref = float(ref_depth)
+    kref = lambda z: int(np.argmin(np.abs(z - ref)))  # (argmin: the first, shallower, of a tie)
+    density = criterion == "density"
+    attrs = {
+        "standard_name": ("ocean_mixed_layer_thickness_defined_by_sigma_theta" if density
+                          else "ocean_mixed_layer_thickness_defined_by_temperature"),
+        "long_name": "Mixed layer depth",
+        "units": "m",
+        "comment": (f"{criterion} threshold relative to the level nearest {ref} m"
+                    + (f"; potential density referenced to {level} m, {eos} equation of state"
+                       if density else "")),
+    }
+    value_attrs = {"units": "kg m-3" if density else "degC"}
+    if density:
+        return _column_depth([thetao, so], threshold, zcoord, kref, "rise", True, "floor", deptho,
+                             "threshold", attrs, value_attrs, eos=_eos_name(eos),
+                             p_ref=(level * 1.0e4) + patm)
+    return _column_depth([thetao], threshold, zcoord, kref, "depart", True, "floor", deptho,
+                         "threshold", attrs, value_attrs)
