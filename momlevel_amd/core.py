@@ -139,16 +139,59 @@ def _query_dtype(dtype):
     return DTYPE_F64 if name == "float64" else DTYPE_F32
 
 
-def _out_like(out, shape, dtype, device, noun=None):
+def _out_like(out, shape, dtype, device, noun=None, name="out"):
     """``out`` when it is a contiguous ``dtype`` tensor of ``shape`` on ``device``; a new one for
-    None.  ``noun``: how the error text names the dtype (default: as torch prints it)."""
+    None.  ``noun``: how the error text names the dtype (default: as torch prints it); ``name``:
+    the argument's name in it."""
+    device = _indexed(device)
     if out is None:
         return torch.empty(shape, dtype=dtype, device=device)
-    if (tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
-            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous {noun or dtype} tensor of shape {tuple(shape)} "
-                         f"on {device}")
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype
+            or out.device != device or not out.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {noun or dtype} tensor of shape "
+                         f"{tuple(shape)} on {device}")
     return out
+
+
+def _indexed(device):
+    """``device`` as tensors report theirs: a bare "cuda" is torch's current device."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        return torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _extent(t):
+    """[first byte, one past the last byte) a kernel addresses through ``t``: from its first to
+    its last element, stride gaps included -- ``numel`` elements for a contiguous tensor, ``(3 - 1)
+    * stride(0) + field`` for the strided variant views of steric_local_decomp.  None for an empty
+    tensor."""
+    if t.numel() == 0:
+        return None
+    last = sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride()))
+    start = t.data_ptr()
+    return start, start + (last + 1) * t.element_size()
+
+
+def _no_overlap(outputs, operands=()):
+    """The result-buffer contract: no output of a launch may share a byte with an
+    operand or with another output -- the kernels take every pointer ``__restrict__``.
+    ``outputs`` / ``operands``: (argument name, tensor or None) pairs of the tensors whose pointers
+    go to the launch, that is after any conversion (a converted copy no longer overlaps).  Raises
+    ``ValueError`` naming both arguments.  Ranges that only touch do not overlap; an empty tensor
+    overlaps nothing; tensors of different devices are different memory.  Host integer
+    arithmetic on pointers, shapes and strides: no device query, no synchronisation."""
+    outputs = [(n, t, _extent(t)) for n, t in outputs if isinstance(t, torch.Tensor)]
+    others = [(n, t, _extent(t)) for n, t in operands if isinstance(t, torch.Tensor)]
+    for i, (oname, o, oext) in enumerate(outputs):
+        if oext is None:
+            continue
+        for xname, x, xext in others + outputs[i + 1:]:
+            if xext is None or x.device != o.device:
+                continue
+            if oext[0] < xext[1] and xext[0] < oext[1]:
+                raise ValueError(f"{oname} overlaps {xname} in memory: a result buffer must not "
+                                 "share bytes with an operand or another result")
 
 
 def _f64(x, device):
@@ -296,10 +339,13 @@ def _k0_call(T, S, p, eos, f32_mode, flags_of, out):
     T, S, nt, nz, ny, nx, sT, sS, dt, squeeze = _pair(T, S, f32_mode)
     pt, p_mode = _pressure(p, nt, nz, ny, nx, T.device, allow4d=True)
     if dt in (DTYPE_T32_S64, DTYPE_T64_S32):
+        if out is not None:
+            raise ValueError("out= is not available for thetao / so of different dtypes")
         return T, S, dt, pt, p_mode, EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, 0, out, squeeze
-    if out is not None and squeeze and out.dim() == 3:
+    if isinstance(out, torch.Tensor) and squeeze and out.dim() == 3:
         out = out.unsqueeze(0)
     out = _out_like(out, (nt, nz, ny, nx), torch.float64, T.device, "float64")
+    _no_overlap([("out", out)], [("thetao", T), ("so", S), ("p", pt)])
     return (T, S, dt, pt, p_mode, EOS_IDS[eos.lower()], nt, nz, ny * nx, sT, sS, flags_of(dt), out,
             squeeze)
 
@@ -331,7 +377,8 @@ def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=No
     """K0: pointwise EOS function over a (nt,nz,ny,nx) or (nz,ny,nx) grid -> float64.
     ``arith``: "exact" | "fused" | None = arith_default("k0", dtype) = exact; applies to the Wright
     density only.  ``out``: a contiguous float64 device tensor of the result's shape to write into
-    (not for thetao / so of different dtypes)."""
+    (not for thetao / so of different dtypes); it must not overlap an operand in memory
+    (``ValueError``)."""
     require_device()
     T, S, dt, pt, p_mode, eid, nt, nz, plane, sT, sS, flags, out, squeeze = _k0_call(
         T, S, p, eos, f32_mode, _k0_flags(eos, func, arith), out)
@@ -339,8 +386,6 @@ def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=No
         # thetao and so of different dtypes: numpy's promotion per sub-expression is the promote
         # kernel's job (one cell per thread over the broadcast operands); exact arithmetic only --
         # an explicit arith="fused" is an error here as it is in K1 / K2
-        if out is not None:
-            raise ValueError("out= is not available for thetao / so of different dtypes")
         _arith_flag(arith, "k0", dt)
         full = (nt, nz) + tuple(T.shape[-2:])
         ny, nx = full[2:]
@@ -357,11 +402,12 @@ def eos_map(T, S, p, eos="wright", func="density", f32_mode="faithful", arith=No
 
 def inverse_barometer(T, S, p, gravity=9.8, eos="wright", f32_mode="faithful", out=None):
     """pso * (-1 / (rho(T,S,pso) * gravity)) on a (nt,nz,ny,nx)/(nz,ny,nx) grid -> float64.
-    ``out``: a contiguous float64 device tensor of the result's shape to write into."""
+    ``out``: a contiguous float64 device tensor of the result's shape to write into; it must not
+    overlap an operand in memory (``ValueError``)."""
     require_device()
     T, S, dt, pt, p_mode, eid, nt, nz, plane, sT, sS, _, out, squeeze = _k0_call(
         T, S, p, eos, f32_mode, lambda dt: 0, out)
-    if out is None:  # (thetao / so of different dtypes: refused by the library below, as before)
+    if out is None:  # (thetao / so of different dtypes: refused by the library below)
         out = torch.empty((nt, nz) + tuple(T.shape[-2:]), dtype=torch.float64, device=T.device)
     _call(_lib.load(), "mlx_inverse_barometer", T.device, _ptr(T), _ptr(S), dt, _ptr(pt), p_mode,
           eid, float(gravity), nt, nz, plane, sT, sS, _ptr(out))
@@ -371,7 +417,7 @@ def inverse_barometer(T, S, p, gravity=9.8, eos="wright", f32_mode="faithful", o
 def _promote_call(T, S, p, eos, func):
     """The operands of one mlx_eos_map_promote call, shared by the launch and by
     eos_map_promote_path: (device, n, keep-alive list, the nine operand arguments, func id, kinds,
-    the PATH_ALIGNED_* bits of the operands)."""
+    the PATH_ALIGNED_* bits of the operands, the (name, tensor) pairs the kernel reads)."""
     import ctypes
 
     if p is None and (eos.lower() != "linear" or func in ("inverse_barometer", "density_ref")):
@@ -381,8 +427,8 @@ def _promote_call(T, S, p, eos, func):
         raise TypeError("at least one operand must be a device tensor")
     device = tensors[0].device
     n = max(int(x.numel()) for x in tensors)
-    keep, args, kinds, aligned = [], [], "", 0
-    bit = {"T": _lib.PATH_ALIGNED_T, "S": _lib.PATH_ALIGNED_S, "p": _lib.PATH_ALIGNED_P}
+    keep, read, args, kinds, aligned = [], [], [], "", 0
+    bit ={"T": _lib.PATH_ALIGNED_T, "S": _lib.PATH_ALIGNED_S, "p": _lib.PATH_ALIGNED_P}
     for name, x in (("T", T), ("S", S), ("p", p)):
         if x is None:
             if name != "p":
@@ -398,6 +444,7 @@ def _promote_call(T, S, p, eos, func):
                 raise ValueError(f"{name} has {x.numel()} elements, expected 1 or {n}")
             x = x.contiguous()
             keep.append(x)
+            read.append((name, x))
             stride = 1 if x.numel() == n and n > 1 else 0
             args += [x.data_ptr(), _lib.KIND_F32 if x.dtype == torch.float32 else _lib.KIND_F64,
                      stride]
@@ -412,7 +459,7 @@ def _promote_call(T, S, p, eos, func):
     fid = _PROMOTE_FUNCS.get(func)
     if fid is None:
         fid = FUNC_IDS[func]
-    return device, n, keep, args, fid, kinds, aligned
+    return device, n, keep, args, fid, kinds, aligned, read
 
 
 def eos_map_promote_path(T, S, p, eos="wright", func="density", out=None):
@@ -420,7 +467,7 @@ def eos_map_promote_path(T, S, p, eos="wright", func="density", out=None):
     (mlx_path_eos_promote on the kinds and the alignment the call itself would pass).  Nothing is
     launched."""
     require_device()
-    _, _, _, _, _, kinds, aligned = _promote_call(T, S, p, eos, func)
+    _, _, _, _, _, kinds, aligned, _ = _promote_call(T, S, p, eos, func)
     return promote_path(kinds, eos, func,
                         aligned | (_lib.PATH_ALIGNED_OUT if out is None or _is16(out) else 0))
 
@@ -434,13 +481,15 @@ def eos_map_promote(T, S, p, eos="wright", func="density", gravity=9.8, out=None
     then carries the constant term RHO_T0_S0 - rho_ref of eos/linear.py:55).  Returns a device tensor of n elements in
     numpy's result dtype (float32 when no float64 array takes part) holding numpy's values.
     ``out``: a contiguous 8-byte aligned device tensor of n elements of that dtype (promote_path
-    tells it) to write into."""
+    tells it) to write into; it must not overlap an operand in memory (``ValueError``; DESIGN.md
+    3.0)."""
     import ctypes
 
     require_device()
-    device, n, keep, args, fid, kinds, _ = _promote_call(T, S, p, eos, func)
+    device, n, keep, args, fid, kinds, _, read = _promote_call(T, S, p, eos, func)
     if out is not None:
         out = _out_like(out, (n,), promote_path(kinds, eos, func)[1], device)
+        _no_overlap([("out", out)], read)
     buf = torch.empty(n, dtype=torch.float64, device=device) if out is None else out
     kind = ctypes.c_int(-1)
     _call(_lib.load(), "mlx_eos_map_promote", device, *args, EOS_IDS[eos.lower()], fid,
@@ -661,10 +710,15 @@ def steric_global_decomp(T, S, T0, S0, vol0, p, eos="wright", f32_mode="faithful
 
 def stream_probe(a, b, out=None):
     """Measurement aid: out = a + b with K2's 16-byte nt loads/stores (16 B read + 8 B written per
-    element); see mlx_stream_probe."""
+    element); see mlx_stream_probe.  ``out``: a contiguous float64 device tensor of a's shape that
+    overlaps neither stream in memory (``ValueError``)."""
     require_device()
-    if out is None:
-        out = torch.empty_like(a)
+    if _float_code(a, "a") != DTYPE_F64 or _float_code(b, "b") != DTYPE_F64:
+        raise TypeError("a and b must be float64")
+    if b.numel() != a.numel() or b.device != a.device:
+        raise ValueError("a and b must agree in size and device")
+    out = _out_like(out, tuple(a.shape), torch.float64, a.device, "float64")
+    _no_overlap([("out", out)], [("a", a), ("b", b)])
     _call(_lib.load(), "mlx_stream_probe", a.device, _ptr(a), _ptr(b), a.numel(), _ptr(out))
     return out
 
@@ -672,13 +726,16 @@ def stream_probe(a, b, out=None):
 def stream_probe_mix(a, b=None, out=None, write=True):
     """Measurement aid: one (``b`` None) or two float32 / float64 streams in, one float64 stream out
     (``write``) or none -- the read:write mix of a held-field / float32 local pass; see
-    mlx_stream_probe_mix.  Returns ``out`` (a 1-element tensor, untouched, when ``write`` is False)."""
+    mlx_stream_probe_mix.  Returns ``out`` (a 1-element tensor, untouched, when ``write`` is False):
+    a contiguous float64 device tensor of a's shape (of one element without ``write``) that overlaps
+    neither stream in memory (``ValueError``)."""
     require_device()
-    dt = _dtype_code(a, "faithful")
-    if b is not None and (b.dtype != a.dtype or b.numel() != a.numel()):
-        raise ValueError("a and b must agree in dtype and size")
-    if out is None:
-        out = torch.empty(a.shape if write else (1,), dtype=torch.float64, device=a.device)
+    dt = _float_code(a, "a")
+    if b is not None and (_float_code(b, "b") != dt or b.numel() != a.numel()
+                          or b.device != a.device):
+        raise ValueError("a and b must agree in dtype, size and device")
+    out = _out_like(out, tuple(a.shape) if write else (1,), torch.float64, a.device, "float64")
+    _no_overlap([("out", out)], [("a", a), ("b", b)])
     _call(_lib.load(), "mlx_stream_probe_mix", a.device, _ptr(a), _ptr(b), dt, a.numel(), _ptr(out),
           int(bool(write)))
     return out
@@ -753,7 +810,10 @@ def _steric_local(entry, T, S, held, rho0m, vol0_surface, p, neg_inv_rhozero, dz
               EOS_IDS[eos.lower()], float(neg_inv_rhozero), nt, nz, ny * nx, sT, sS, flags,
               *outputs)
 
-    return dev, (nt, nz, ny, nx), launch
+    read = [("thetao", T), ("so", S)] + list(zip(("T0", "S0"), held or ())) + [
+        ("rho0m", rho0m), ("vol0_surface", vol0_surface), ("dz", dz), ("z_i", z_i),
+        ("deptho", deptho), ("p", pt)]
+    return dev, (nt, nz, ny, nx), launch, read
 
 
 def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=None,
@@ -765,25 +825,20 @@ def steric_local(T, S, rho0m, vol0_surface, p, neg_inv_rhozero, dz=None, z_i=Non
     ``delta_rho_dtype`` torch.float32 (an extension; the default is float64): the kernel rounds each
     delta_rho value to float32 right before storing it -- ``float32(float64 delta_rho)`` bit for
     bit, half the bytes -- while eta is summed from the unrounded terms and stays float64, the
-    same bits as without it.  A ``delta_rho_out`` must be of that dtype."""
+    same bits as without it.  A ``delta_rho_out`` must be of that dtype.
+    ``delta_rho_out`` (nt,nz,ny,nx) / ``eta_out`` (nt,ny,nx) float64: contiguous device tensors of
+    exactly these shapes that overlap neither an operand nor each other in memory (``ValueError``;
+    DESIGN.md 3.0)."""
     ddt = _delta_rho_dtype(delta_rho_dtype)
-    dev, (nt, nz, ny, nx), launch = _steric_local(
+    dev, (nt, nz, ny, nx), launch, read = _steric_local(
         "mlx_steric_local", T, S, None, rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i, deptho,
         eos, f32_mode, skip_dry, arith, ddt if want_delta_rho else torch.float64)
     drho = None
     if want_delta_rho:
-        drho = delta_rho_out
-        if drho is None:
-            drho = torch.empty((nt, nz, ny, nx), dtype=ddt, device=dev)
-        elif (drho.dtype != ddt or drho.numel() < nt * nz * ny * nx or drho.device != dev
-              or not drho.is_contiguous()):
-            # (never a silent reinterpretation of the buffer's elements)
-            raise ValueError(f"delta_rho_out must be a contiguous {ddt} tensor of {(nt, nz, ny, nx)} "
-                             f"on {dev} (delta_rho_dtype={ddt}), not {drho.dtype} "
-                             f"{tuple(drho.shape)}")
-    eta = eta_out if eta_out is not None else torch.empty(
-        (nt, ny, nx), dtype=torch.float64, device=dev
-    )
+        # (never a silent reinterpretation of the buffer's elements: delta_rho_dtype decides)
+        drho = _out_like(delta_rho_out, (nt, nz, ny, nx), ddt, dev, name="delta_rho_out")
+    eta = _out_like(eta_out, (nt, ny, nx), torch.float64, dev, "float64", name="eta_out")
+    _no_overlap([("delta_rho_out", drho), ("eta_out", eta)], read)
     launch(_ptr(drho), _ptr(eta))
     return drho, eta
 
@@ -799,15 +854,18 @@ def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, d
     eta (3,nt,ny,nx)), variant order LOCAL_DECOMP_ROWS; each field bit-identical to its
     steric_local call.  ``delta_rho_out`` / ``eta_out``: optional (3, nt, ...) float64 device
     tensors (or views whose variant axis has any stride, e.g. ``full[:, t0:t1]``).
-    ``delta_rho_dtype``: as in steric_local (``delta_rho_out`` then float32; eta stays float64)."""
+    ``delta_rho_dtype``: as in steric_local (``delta_rho_out`` then float32; eta stays float64).
+    Neither output may overlap an operand or the other output in memory, over the whole extent from
+    its first variant to its last, stride gaps included (``ValueError``)."""
     ddt = _delta_rho_dtype(delta_rho_dtype)
-    dev, (nt, nz, ny, nx), launch = _steric_local(
+    dev, (nt, nz, ny, nx), launch, read = _steric_local(
         "mlx_steric_local_decomp", T, S, (T0, S0), rho0m, vol0_surface, p, neg_inv_rhozero, dz, z_i,
         deptho, eos, f32_mode, skip_dry, arith, ddt if want_delta_rho else torch.float64)
 
     def variant_major(x, shape, dtype=torch.float64):
         """(3, nt, ...) device tensor of ``dtype`` whose per-variant fields are contiguous"""
-        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
+        if (not isinstance(x, torch.Tensor) or tuple(x.shape) != shape or x.dtype != dtype
+                or x.device != dev):
             raise ValueError(f"output must be a {dtype} {shape} tensor on {dev}")
         if not x[0].is_contiguous() or x.stride(0) < x[0].numel():
             raise ValueError("each variant's field must be contiguous")
@@ -821,6 +879,7 @@ def steric_local_decomp(T, S, T0, S0, rho0m, vol0_surface, p, neg_inv_rhozero, d
     eta = eta_out if eta_out is not None else torch.empty((3, nt, ny, nx), dtype=torch.float64,
                                                            device=dev)
     variant_major(eta, (3, nt, ny, nx))
+    _no_overlap([("delta_rho_out", drho), ("eta_out", eta)], read)
     launch(_ptr(drho), drho.stride(0) if drho is not None else 0, _ptr(eta), eta.stride(0))
     return drho, eta
 
@@ -865,7 +924,9 @@ def masso(rho, vol):
 
 def group_weighted_mean(x, w, group_len, out=None):
     """Per-group weighted mean over the leading axis (annual_average's arithmetic): x (nt, ...)
-    with nt = ngroups*group_len, w (nt,) -> (ngroups, ...); NaNs carry no weight."""
+    with nt = ngroups*group_len, w (nt,) -> (ngroups, ...); NaNs carry no weight.  ``out``: a
+    contiguous float64 device tensor of that shape that overlaps neither x nor w in memory
+    (``ValueError``)."""
     require_device()
     x = _f64(x, x.device)
     w = _f64(w, x.device).reshape(-1)
@@ -874,8 +935,8 @@ def group_weighted_mean(x, w, group_len, out=None):
         raise ValueError("the time axis must hold whole groups and one weight per step")
     ngroups = nt // group_len
     n = x[0].numel()
-    if out is None:
-        out = torch.empty((ngroups,) + tuple(x.shape[1:]), dtype=torch.float64, device=x.device)
+    out = _out_like(out, (ngroups,) + tuple(x.shape[1:]), torch.float64, x.device, "float64")
+    _no_overlap([("out", out)], [("x", x), ("w", w)])
     _call(_lib.load(), "mlx_group_weighted_mean", x.device, _ptr(x), _ptr(w), ngroups, group_len, n,
           _ptr(out))
     return out
@@ -954,7 +1015,9 @@ def time_apply(y, mode, xm, a, b=None, out=None):
     """The elementwise pass (mlx_time_apply).  Straight-line modes "remove" / "correct" /
     "trend" / "trend_anom": xm = x (nt,), a = slope, b = intercept ("remove").  Model modes
     "model_resid" / "model": xm = M (K, nt), a = coef (K, ...).  ``y`` (nt, ...) may be None in the
-    modes that do not read it.  Returns (nt, ...) float64."""
+    modes that do not read it.  Returns (nt, ...) float64 (``out`` when given: a contiguous
+    float64 device tensor of that shape that overlaps no operand in memory; ``ValueError``
+    otherwise)."""
     require_device()
     lib = _lib.load_trend()
     code_mode = APPLY_MODES[mode]
@@ -984,8 +1047,8 @@ def time_apply(y, mode, xm, a, b=None, out=None):
             raise ValueError("slope and intercept must agree in shape")
     else:
         b = None
-    if out is None:
-        out = torch.empty((nt,) + cells_shape, dtype=torch.float64, device=device)
+    out = _out_like(out, (nt,) + cells_shape, torch.float64, device, "float64")
+    _no_overlap([("out", out)], [("y", y), ("xm", xm), ("a", a), ("b", b)])
     if n == 0:
         return out
     step = 65535 * 64  # the kernel's grid.y carries the time axis in windows of 64 steps
@@ -1050,7 +1113,9 @@ def time_group_stat(y, steps, offsets=None, stat="mean", out=None):
     ``steps`` / ``offsets`` are host integer sequences, checked here before they are uploaded, or
     ``steps`` is a ``DeviceGroups`` made by ``upload_groups`` (``offsets`` None).  float64 results
     are bit-identical to numpy's nanmean / nanstd / nanmin / nanmax over axis 0 of ``y[sel]``;
-    float32 records are accumulated in float64 and rounded once."""
+    float32 records are accumulated in float64 and rounded once.  ``out``: a contiguous device
+    tensor of the result's shape and dtype that overlaps no operand in memory (``ValueError``;
+    DESIGN.md 3.0)."""
     require_device()
     lib = _lib.load_clim()
     if stat not in STAT_IDS:
@@ -1066,6 +1131,7 @@ def time_group_stat(y, steps, offsets=None, stat="mean", out=None):
         groups = DeviceGroups(steps, offsets, nt, y.device)
     shape = (groups.ngroups,) + tuple(y.shape[1:])
     out = _out_like(out, shape, y.dtype, y.device)
+    _no_overlap([("out", out)], [("y", y), ("steps", groups.steps), ("offsets", groups.offsets)])
     if n == 0:
         return out
     _call(lib, "mlx_clim_group_stat", y.device, _ptr(y), code, _ptr(groups.steps),
@@ -1164,7 +1230,9 @@ def gauge_nearest(points, gauges, split=0):
 def gauge_gather(y, index, out=None):
     """``out[g, r] = y[r, index[g]]`` (mlx_gauge_gather): y (nrest, n) float32 / float64 on the
     device, ``index`` (ng) integers (host sequence or device tensor)  ->  (ng, nrest) of y's dtype,
-    each gauge's series contiguous, bits copied.  An index outside [0, n) gives a NaN series."""
+    each gauge's series contiguous, bits copied.  An index outside [0, n) gives a NaN series.
+    ``out``: a contiguous device tensor of that shape and dtype that overlaps neither y nor a
+    device ``index`` in memory (``ValueError``)."""
     require_device()
     lib = _lib.load_gauge()
     if isinstance(y, torch.Tensor) and y.is_cuda:
@@ -1185,6 +1253,7 @@ def gauge_gather(y, index, out=None):
     ng = index.numel()
     shape = (ng, nrest)
     out = _out_like(out, shape, y.dtype, y.device)
+    _no_overlap([("out", out)], [("y", y), ("index", index)])
     if ng == 0 or nrest == 0:
         return out
     if n == 0:
@@ -1196,8 +1265,8 @@ def gauge_gather(y, index, out=None):
 def spice_map(theta, so, out=None):
     """Flament (2002) spiciness of every cell (mlx_spice_map): ``theta`` and ``so`` contiguous 1-D
     device tensors of equal length, each float32 or float64 on its own  ->  a float64 device tensor
-    of that length (``out`` when given).  float32 values are widened exactly; all arithmetic is
-    float64."""
+    of that length (``out`` when given; it must not overlap an operand in memory: ``ValueError``,
+    DESIGN.md 3.0).  float32 values are widened exactly; all arithmetic is float64."""
     require_device()
     lib = _lib.load_spice()
     tdt, sdt = _float_code(theta, "theta", 1), _float_code(so, "so", 1)
@@ -1205,6 +1274,7 @@ def spice_map(theta, so, out=None):
         raise ValueError("theta and so must agree in length and device")
     n = theta.numel()
     out = _out_like(out, (n,), torch.float64, theta.device, "float64")
+    _no_overlap([("out", out)], [("theta", theta), ("so", so)])
     _call(lib, "mlx_spice_map", theta.device, _ptr(theta), tdt, _ptr(so), sdt, n, _ptr(out))
     return out
 
@@ -1231,7 +1301,9 @@ def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
     is (nrec, ny - s, nx) and ``v`` (nrec, ny, nx - s), both of ONE dtype; ``dx`` / ``dy`` are their
     2-D metrics, of one dtype with ``area``.  All contiguous device tensors, float32 or float64.
     Returns (nrec, ny, nx): float32 when fields and metrics are all float32, float64 otherwise --
-    bit for bit what numpy gives operator for operator."""
+    bit for bit what numpy gives operator for operator.  ``out``: a contiguous device tensor of
+    that shape and dtype that overlaps no operand in memory -- the stencil reads its neighbours'
+    cells (``ValueError``)."""
     require_device()
     lib = _lib.load_vort()
     fdt = _float_code(u, "u", 3)
@@ -1257,6 +1329,7 @@ def rel_vort(u, v, dx, dy, area, symmetric=False, out=None):
         raise ValueError("u, v, dx, dy and area must live on one device")
     odt = torch.float32 if fdt == DTYPE_F32 and mdt == DTYPE_F32 else torch.float64
     out = _out_like(out, (nrec, ny, nx), odt, u.device)
+    _no_overlap([("out", out)], [("u", u), ("v", v), ("dx", dx), ("dy", dy), ("area", area)])
     _call(lib, "mlx_vort_rel_vort", u.device, _ptr(u), _ptr(v), fdt, _ptr(dx), _ptr(dy), _ptr(area),
           mdt, nrec, ny, nx, s, _ptr(out))
     return out
@@ -1272,7 +1345,8 @@ def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=
     live on the corner plane; ``n2`` is (nrec, ny, nx) without ``interp`` and (nrec, ny - s, nx - s)
     with it (s = int(symmetric)): then n2c is N^2 averaged along x and then along y with zero
     padding, inside the pass.  Each operand float32 or float64 on its own; the result has numpy's
-    promotion of the three, and numpy's bits."""
+    promotion of the three, and numpy's bits.  ``out``: a contiguous device tensor of the result's
+    shape and dtype that overlaps no operand in memory (``ValueError``)."""
     if units not in VORT_UNITS:
         raise ValueError(f"unknown units option `{units}`")
     require_device()
@@ -1295,6 +1369,7 @@ def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=
         raise ValueError("zeta, coriolis and n2 must live on one device")
     odt = torch.float32 if (zdt, cdt, ndt) == (DTYPE_F32,) * 3 else torch.float64
     out = _out_like(out, (nrec, ny, nx), odt, zeta.device)
+    _no_overlap([("out", out)], [("zeta", zeta), ("coriolis", coriolis), ("n2", n2)])
     _call(lib, "mlx_vort_pv", zeta.device, _ptr(zeta), zdt, _ptr(coriolis), cdt, _ptr(n2), ndt,
           nrec, ny, nx, interp, s, float(gravity), VORT_UNITS[units], _ptr(out))
     return out
@@ -1303,7 +1378,9 @@ def potential_vorticity(zeta, coriolis, n2, gravity=9.8, interp=True, symmetric=
 def rossby_radius(c, f, out=None):
     """``c / abs(f)`` (mlx_vort_rossby): ``c`` a contiguous (outer, plane, inner) device tensor, ``f``
     a contiguous tensor of ``plane`` elements, each float32 or float64; IEEE division, so that
-    ``f == 0`` gives the +-inf / NaN numpy gives."""
+    ``f == 0`` gives the +-inf / NaN numpy gives.  ``out``: a contiguous device tensor of c's shape
+    (float32 when both are float32, else float64) that overlaps neither in memory (``ValueError``;
+    DESIGN.md 3.0)."""
     require_device()
     lib = _lib.load_vort()
     cdt, fdt = _float_code(c, "c", 3), _float_code(f, "f")
@@ -1312,6 +1389,7 @@ def rossby_radius(c, f, out=None):
         raise ValueError(f"f must hold {plane} elements on {c.device}")
     odt = torch.float32 if (cdt, fdt) == (DTYPE_F32, DTYPE_F32) else torch.float64
     out = _out_like(out, (outer, plane, inner), odt, c.device)
+    _no_overlap([("out", out)], [("c", c), ("f", f)])
     _call(lib, "mlx_vort_rossby", c.device, _ptr(c), cdt, _ptr(f), fdt, outer, plane, inner,
           _ptr(out))
     return out
@@ -1376,7 +1454,8 @@ def area_mean(v, area, slot=None, nslots=1):
 def area_anomaly(v, mean, slot=None, out=None):
     """``v.astype(float64) - mean[rec, slot]`` (mlx_area_anomaly): ``v`` (nrec, plane) float32 or
     float64, ``mean`` (nrec, nslots) float64, ``slot`` as in area_mean (any number of slots); cells
-    of no slot give NaN.  Returns (nrec, plane) float64 (``out`` when given)."""
+    of no slot give NaN.  Returns (nrec, plane) float64 (``out`` when given; it must not overlap
+    an operand in memory: ``ValueError``)."""
     require_device()
     lib = _lib.load_area()
     vdt = _float_code(v, "v", 2)
@@ -1389,6 +1468,7 @@ def area_anomaly(v, mean, slot=None, out=None):
         raise ValueError("mean must hold at least one slot")
     _area_slot(slot, nslots, plane, v.device)
     out = _out_like(out, (nrec, plane), torch.float64, v.device, "float64")
+    _no_overlap([("out", out)], [("v", v), ("mean", mean), ("slot", slot)])
     _call(lib, "mlx_area_anomaly", v.device, _ptr(v), vdt, _ptr(slot), nslots, _ptr(mean), nrec,
           plane, _ptr(out))
     return out
@@ -1427,7 +1507,8 @@ def layer_integral(x, z_i, depth, tops, bottoms, surface=None, scale=1.0, out=No
     ``x`` (nrec, nz, plane) contiguous float32 / float64 device tensor; ``z_i`` the nz+1 interfaces;
     ``depth`` (plane), NaN = land; ``tops`` / ``bottoms`` host sequences of equal length, a bottom
     of +inf (or None) meaning the sea floor; ``surface`` None or (plane): NaN there gives NaN.
-    Returns (nrec, nl, plane) float64 (``out`` when given).  More than LAYER_MAX layers run as
+    Returns (nrec, nl, plane) float64 (``out`` when given; it must not overlap an operand in
+    memory: ``ValueError``).  More than LAYER_MAX layers run as
     several launches over groups of layers; every layer gets the bits it would get alone."""
     require_device()
     lib = _lib.load_layer()
@@ -1450,6 +1531,7 @@ def layer_integral(x, z_i, depth, tops, bottoms, surface=None, scale=1.0, out=No
         if surface.numel() != plane:
             raise ValueError(f"surface must hold {plane} cells")
     out = _out_like(out, (nrec, nl, plane), torch.float64, dev, "float64")
+    _no_overlap([("out", out)], [("x", x), ("z_i", z_i), ("depth", depth), ("surface", surface)])
     groups = layer_groups(nl)
     for start, count in groups:
         part = out if len(groups) == 1 else torch.empty((nrec, count, plane), dtype=torch.float64,
@@ -1497,7 +1579,8 @@ def column_crossing(a, z, targets, b=None, kref=0, mode="rise", relative=False, 
     level; ``mode`` "rise" | "fall" | "depart"; ``relative``: targets are offsets from the value at
     ``kref``; ``miss`` "nan" | "floor": what a column without a crossing gets (``floor`` (plane)
     when given, else the depth of its deepest level with a value).  Returns (nrec, ntargets,
-    plane) float64 (``out`` when given).  More than COLUMN_MAX_TARGETS targets run as several
+    plane) float64 (``out`` when given; it must not overlap an operand in memory: ``ValueError``,
+    DESIGN.md 3.0).  More than COLUMN_MAX_TARGETS targets run as several
     launches over groups of targets; every target gets the bits it would get alone."""
     require_device()
     lib = _lib.load_column()
@@ -1525,6 +1608,7 @@ def column_crossing(a, z, targets, b=None, kref=0, mode="rise", relative=False, 
         if floor.numel() != plane:
             raise ValueError(f"floor must hold {plane} cells")
     out = _out_like(out, (nrec, nt, plane), torch.float64, dev, "float64")
+    _no_overlap([("out", out)], [("a", a), ("b", b), ("z", z), ("floor", floor)])
     groups = layer_groups(nt, COLUMN_MAX_TARGETS)
     for start, count in groups:
         part = out if len(groups) == 1 else torch.empty((nrec, count, plane), dtype=torch.float64,
@@ -1589,7 +1673,9 @@ def time_filter(y, w, lead, min_count=None, normalise=False, out=None, out_dtype
     device tensor of one of those shapes (its values are the caller's); ``0 <= lead < W``.  A step
     is valid when it lies in the record and is not NaN; fewer than ``min_count`` (default W) valid
     steps give NaN; ``normalise`` divides by the sum of the valid steps' weights.  Returns
-    (nt, ...) of ``out_dtype`` (default y's dtype; float32 is the float64 result rounded once)."""
+    (nt, ...) of ``out_dtype`` (default y's dtype; float32 is the float64 result rounded once).
+    ``out``: a contiguous device tensor of that shape and dtype that overlaps neither y nor device
+    weights in memory -- an output step reads W input steps (``ValueError``)."""
     require_device()
     lib = _lib.load_filter()
     y, nt, n, code = _time_record(y)
@@ -1614,6 +1700,7 @@ def time_filter(y, w, lead, min_count=None, normalise=False, out=None, out_dtype
     if out_dtype not in (torch.float32, torch.float64):
         raise TypeError(f"out_dtype must be float32 or float64, got {out_dtype}")
     out = _out_like(out, tuple(y.shape), out_dtype, y.device)
+    _no_overlap([("out", out)], [("y", y), ("w", wd)])
     if n == 0:
         return out
     _call(lib, "mlx_filter_apply", y.device, _ptr(y), code, _ptr(wd), W, W if wd.dim() == 2 else 0,
@@ -1675,7 +1762,9 @@ def time_quantile(y, q, steps=None, offsets=None, out=None):
     ``DeviceGroups``); ``steps`` None: one group of all rows.  float64 results are value-identical
     to ``numpy.nanquantile(y[sel], q, axis=0)`` (tests/quantile_numpy.py restates the contract);
     float32 records are selected and interpolated in float64 and rounded once.  Any number of
-    levels: the kernel takes ``QUANTILE_MAX_Q`` a launch."""
+    levels: the kernel takes ``QUANTILE_MAX_Q`` a launch.  ``out``: a contiguous device tensor of
+    the result's shape and dtype that overlaps no operand in memory (``ValueError``; DESIGN.md
+    3.0)."""
     require_device()
     lib = _lib.load_quantile()
     levels = quantile_levels(q)
@@ -1683,6 +1772,8 @@ def time_quantile(y, q, steps=None, offsets=None, out=None):
     sp, op, nsel, ngroups, _keep = _quantile_groups(nt, y, steps, offsets)
     shape = (int(levels.size), ngroups) + tuple(y.shape[1:])
     out = _out_like(out, shape, y.dtype, y.device)
+    _no_overlap([("out", out)], [("y", y), ("steps", getattr(_keep, "steps", None)),
+                                 ("offsets", getattr(_keep, "offsets", None))])
     if n == 0:
         return out
     for c0 in range(0, levels.size, _lib.QUANTILE_MAX_Q):
@@ -1729,15 +1820,19 @@ def calc_dz(z_i, depth, top=0.0, bottom=None, fraction=False):
 
 def synth_field(shape, dtype=torch.float64, *, seed, field_id, lo, scale, mask3d=None,
                 t0=0, global_hw=None, origin=(0, 0), device="cuda", out=None):
-    """Counter-based synthetic field (bench / full-size tests); see synthetic.py."""
+    """Counter-based synthetic field (bench / full-size tests); see synthetic.py.  ``out``: a
+    contiguous tensor of exactly ``shape``, ``dtype`` and ``device`` that does not overlap
+    ``mask3d`` in memory (``ValueError``)."""
     require_device()
-    nt, nz, ny, nx = shape
+    nt, nz, ny, nx = (int(v) for v in shape)
     NY, NX = global_hw if global_hw is not None else (ny, nx)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=device)
-    code = DTYPE_F64 if out.dtype == torch.float64 else DTYPE_F32
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"dtype must be float32 or float64, got {dtype}")
+    out = _out_like(out, (nt, nz, ny, nx), dtype, device)
+    code = DTYPE_F64 if dtype == torch.float64 else DTYPE_F32
     if mask3d is not None:
         mask3d = _f64(mask3d, out.device)
+    _no_overlap([("out", out)], [("mask3d", mask3d)])
     _call(_lib.load(), "mlx_synth_field", out.device, _ptr(out), code, nt, nz, ny, nx, t0, NY, NX,
           origin[0], origin[1], seed, field_id, float(lo), float(scale), _ptr(mask3d))
     return out
