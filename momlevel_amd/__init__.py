@@ -8,7 +8,7 @@ detrend and deseason fits of ``trend``, and the grouped time statistics
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
 include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
-include/momlevel_quantile.h, include/momlevel_column.h).
+include/momlevel_quantile.h, include/momlevel_column.h, include/momlevel_eof.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -52,6 +52,12 @@ depth by a density or temperature threshold, the depth of the 20 degC isotherm, 
 sigma0 = 27 -- one search down every column that stops reading at the crossing, the potential
 density evaluated inside it and never written out (include/momlevel_column.h).
 
+``eof`` (an EXTENSION too) couples all cells of a ``(time, yh, xh)`` record: ``time_covariance``,
+``calc_eofs`` (eigenvalues, variance fractions, unit-variance principal components and the EOFs as
+covariance maps) and ``project_field``.  The contraction over the cells runs on the float64 matrix
+cores with the anomalies formed while the rows are staged, in a fixed order of summation; the
+``nt x nt`` eigen-problem is solved on the host (include/momlevel_eof.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -62,6 +68,7 @@ __version__ = "0.1.0"
 
 from . import derived
 from . import dynamic
+from . import eof
 from . import eos
 from . import extremes
 from . import filters
@@ -93,6 +100,7 @@ __all__ = [
     "derived",
     "dynamic",
     "inverse_barometer",
+    "eof",
     "eos",
     "extremes",
     "filters",

@@ -56,6 +56,8 @@ QUANTILE_MAX_Q = 8
 COLUMN_MAX_TARGETS = 8
 COLUMN_RISE, COLUMN_FALL, COLUMN_DEPART = 0, 1, 2
 COLUMN_MISS_NAN, COLUMN_MISS_FLOOR = 0, 1
+# ---- constants mirrored from include/momlevel_eof.h --------------------------------
+GRAM_MAX_SPLIT = 32
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -249,6 +251,19 @@ COLUMN_SIGNATURES = {
 }
 
 
+# The time Gram matrix behind the EOFs (include/momlevel_eof.h): bound by load_eof() on first use,
+# for the same reason.  (Not named *_SIGNATURES: tests/test_column_host.py counts the tables of that
+# name, eleven beside its own.)
+EOF_PROTOTYPES = {
+    "mlx_gram_tile": (_int, []),
+    "mlx_gram_cells": (_i64, [_i64]),
+    "mlx_gram_matrix_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mlx_gram_matrix": (_int, [_vp, _int, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz,
+                             _vp]),
+    "mlx_gram_issue_probe": (_int, [_i64, _i64, _vp, ctypes.POINTER(ctypes.c_int64), _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -327,12 +342,13 @@ _GROUPS = {
     "path": (PATH_SIGNATURES, "the path queries of the EOS maps"),
     "quantile": (QUANTILE_SIGNATURES, "the quantile kernels"),
     "column": (COLUMN_SIGNATURES, "the column-search kernel"),
+    "eof": (EOF_PROTOTYPES, "the Gram kernels"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
-_layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = False
+_layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = _eof_bound = False
 
 
 def _load_group(group):
@@ -388,6 +404,10 @@ def load_quantile():
 
 def load_column():
     return _load_group("column")
+
+
+def load_eof():
+    return _load_group("eof")
 
 
 def last_error():

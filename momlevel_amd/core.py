@@ -1475,6 +1475,88 @@ def area_anomaly(v, mean, slot=None, out=None):
 
 
 # ---------------------------------------------------------------------------------------
+# the time Gram matrix behind the EOFs (include/momlevel_eof.h; csrc/momlevel_eof.hip)
+# ---------------------------------------------------------------------------------------
+GRAM_MAX_SPLIT = _lib.GRAM_MAX_SPLIT  # the most ranges the cells of a time_gram call are cut into
+
+
+def gram_tile():
+    """Rows (and columns) of G one block of mlx_gram_matrix owns (mlx_gram_tile)."""
+    return int(_lib.load_eof().mlx_gram_tile())
+
+
+def gram_cells(n):
+    """Cells of one block's range for a record of ``n`` cells (mlx_gram_cells): the partial sums of
+    ``ceil(n / gram_cells(n))`` ranges are added in ascending order, so the order of summation is a
+    function of ``n`` alone.  0 for n < 1."""
+    return int(_lib.load_eof().mlx_gram_cells(int(n)))
+
+
+def _gram_map(x, n, device, name):
+    """a per-cell float64 map of a time_gram call, or None"""
+    if x is None:
+        return None
+    if _float_code(x, name) != DTYPE_F64:
+        raise TypeError(f"{name} must be float64")
+    if x.numel() != n or x.device != device:
+        raise ValueError(f"{name} must hold {n} elements on {device}")
+    return x
+
+
+def time_gram(y1, y2=None, center1=None, center2=None, scale=None):
+    """G[s, t] = sum_c b1[s, c] * b2[t, c] with b = (y - center) * scale per cell, 0 in a cell whose
+    center1, center2 or scale is NaN (mlx_gram_matrix): ``y1`` (nt1, ...) and ``y2`` (nt2, ...)
+    float32 / float64 device records over the same cells, the maps contiguous float64 device
+    tensors of one element per cell or None (center 0, scale 1).  Returns a new (nt1, nt2) float64
+    device tensor.  ``y2=None`` is the symmetric form (``center2`` must be None too): b2 = b1, the
+    tiles above the diagonal computed once, ``G == G.T`` to the bit.  Fixed order of summation on
+    the float64 matrix cores, no atomics: two runs agree to the bit, and G[s, t] depends on the rows
+    s and t and on the number of cells alone."""
+    require_device()
+    lib = _lib.load_eof()
+    y1, nt1, n, code1 = _time_record(y1)
+    dev = y1.device
+    if y2 is None:
+        if center2 is not None:
+            raise ValueError("center2 belongs to y2: the symmetric form takes center1 only")
+        nt2, code2, ncols = 0, code1, nt1
+    else:
+        y2, nt2, n2, code2 = _time_record(y2)
+        if n2 != n or y2.device != dev:
+            raise ValueError(f"y2 must hold {n} cells a step on {dev}")
+        ncols = nt2
+    if n < 1:
+        raise ValueError("the record holds no cells")
+    center1 = _gram_map(center1, n, dev, "center1")
+    center2 = _gram_map(center2, n, dev, "center2")
+    scale = _gram_map(scale, n, dev, "scale")
+    nbytes = int(lib.mlx_gram_matrix_workspace_bytes(nt1, nt2, n))
+    if nbytes == 0:
+        raise ValueError(f"records of {nt1} and {ncols} steps x {n} cells are outside the Gram "
+                         "kernel's range")
+    G = torch.empty((nt1, ncols), dtype=torch.float64, device=dev)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    _call(lib, "mlx_gram_matrix", dev, _ptr(y1), code1, _ptr(center1), nt1, _ptr(y2), code2,
+          _ptr(center2), nt2, _ptr(scale), n, _ptr(G), _ptr(ws), nbytes)
+    return G
+
+
+def gram_issue_probe(iters=4096, blocks=1024, device="cuda"):
+    """Measurement aid: enqueue the issue-rate probe of v_mfma_f64_16x16x4_f64
+    (mlx_gram_issue_probe) on ``device``'s current stream; returns the floating-point operations
+    of the launch."""
+    require_device()
+    import ctypes
+
+    device = _indexed(device)
+    sink = torch.empty(int(blocks) * 256, dtype=torch.float64, device=device)
+    flop = ctypes.c_int64(0)
+    _call(_lib.load_eof(), "mlx_gram_issue_probe", device, int(iters), int(blocks), _ptr(sink),
+          ctypes.byref(flop))
+    return int(flop.value)
+
+
+# ---------------------------------------------------------------------------------------
 # depth-layer sums (include/momlevel_layer.h; csrc/momlevel_layer.hip)
 # ---------------------------------------------------------------------------------------
 LAYER_MAX = _lib.LAYER_MAX  # layers per launch of layer_integral

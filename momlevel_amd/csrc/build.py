@@ -36,6 +36,8 @@ FEATURES = {
     "quantile": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
                  "include/momlevel_quantile.h"],
     "column": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_column.h"],
+    "eof": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
+            "include/momlevel_eof.h"],
 }
 
 
@@ -153,6 +155,11 @@ def quantile_source_sha():
 def column_source_sha():
     """the column-search kernel's own guard: csrc/momlevel_column.hip (+ what it includes, + flags)"""
     return feature_source_sha("column")
+
+
+def eof_source_sha():
+    """the Gram kernels' own guard: csrc/momlevel_eof.hip (+ what it includes, + flags)"""
+    return feature_source_sha("eof")
 
 
 def hipcc():
