@@ -8,10 +8,8 @@ group.  Here the host makes only what depends on the time axis alone -- a *plan*
 which group (``steps`` / ``offsets``) and the new time axis -- and one HIP pass over the record
 (csrc/momlevel_clim.hip, ``core.time_group_stat``) reduces every group of every cell.
 
-Placement is the trend module's (``trend._Record``): a device tensor in gives a device tensor out
-and nothing crosses the host link; host (or lazily read) arrays go up and the results come down
-through ``hostio``, a block of cells at a time when the record does not fit the device.  A group is
-never split between threads, so the block size never changes a bit of the result.
+Placement is the record module's (``record.Record``): device in, device out; host arrays in blocks
+of cells.  A group is never split between threads, so the block size never changes a bit.
 
 Arithmetic: float64 results are bit-identical to numpy's nanmean / nanstd (ddof = 0) / nanmin /
 nanmax over axis 0 of the selected rows.  float32 records keep their dtype: they are accumulated in
@@ -22,9 +20,9 @@ max, where xarray keeps the integer dtype.  float16 and long double records are 
 
 import numpy as np
 
-from . import cftime_lite
+from . import cftime_lite, record
 from .cftime_lite import DatetimeLite
-from .labeled import _UNSUPPORTED, DataArray, Dataset, dtype_name, np_dtype
+from .labeled import DataArray
 
 __all__ = ["GroupPlan", "monthly_plan", "annual_cycle_plan", "yearly_plan", "grouped_stat"]
 
@@ -146,46 +144,6 @@ def yearly_plan(time_da, tcoord="time"):
     return GroupPlan(members, _like_axis(points, values[0]), tcoord)
 
 
-def _check_record_dtype(da):
-    name = dtype_name(da.data.dtype)
-    if name in _UNSUPPORTED:
-        raise TypeError(f"{name} records are not supported: convert '{da.name}' to float32 or "
-                        "float64")
-    return name
-
-
-def _is_numeric(da):
-    """float, integer and boolean variables take part; strings, objects, times are skipped"""
-    if dtype_name(da.data.dtype) in _UNSUPPORTED:
-        return True  # (and refused, loudly, by _check_record_dtype)
-    try:
-        return np_dtype(da.data.dtype).kind in "fiub"
-    except TypeError:
-        return False
-
-
-def _stat_array(da, tcoord, plan, stat):
-    """one DataArray: the record with ``tcoord`` leading, reduced group by group on the device"""
-    from . import core
-    from .trend import _Record
-
-    _check_record_dtype(da)
-    rec = _Record(da, tcoord)
-    uploaded = {}
-
-    def block(y):
-        if y.device not in uploaded:
-            uploaded[y.device] = core.upload_groups(plan.steps, plan.offsets, rec.nt, y.device)
-        return (core.time_group_stat(y, uploaded[y.device], stat=stat),)
-
-    (res,) = rec.walk(block, 0, plan.ngroups)
-    coords = {k: v for k, v in da.coords.items() if tcoord not in v.dims}
-    coords[tcoord] = plan.time
-    out = DataArray(res, (tcoord,) + rec.rest_dims, coords, da.attrs, da.name)
-    out.encoding = dict(da.encoding)
-    return out
-
-
 def grouped_stat(xobj, tcoord, plan, stat):
     """``stat`` over the groups of ``plan`` for a DataArray, or for every numeric variable of a
     Dataset that has ``tcoord``.  Results have ``tcoord`` leading.  Dataset: non-numeric variables
@@ -194,19 +152,20 @@ def grouped_stat(xobj, tcoord, plan, stat):
     carried."""
     if stat not in STATS:
         raise ValueError(f"stat must be one of {STATS}, got '{stat}'")
-    if isinstance(xobj, DataArray):
-        if tcoord not in xobj.dims:
-            raise ValueError(f"the array has no dimension '{tcoord}'")
-        return _stat_array(xobj, tcoord, plan, stat)
-    if isinstance(xobj, Dataset):
-        result = Dataset()
-        for name, c in xobj.coords.items():
-            if tcoord not in c.dims:
-                result._set(name, c, is_coord=True)
-        result._set(tcoord, plan.time, is_coord=True)
-        for name, var in xobj.data_vars.items():
-            if tcoord not in var.dims or not _is_numeric(var):
-                continue
-            result[name] = _stat_array(var, tcoord, plan, stat)
-        return result
-    raise TypeError("Input must be a DataArray or a Dataset")
+
+    def one(da):
+        """the record with ``tcoord`` leading, reduced group by group on the device"""
+        from . import core
+
+        record.check_record_dtype(da)
+        rec = record.Record(da, tcoord)
+        groups = record.plan_groups(plan, rec.nt)
+
+        def block(y, _cells):
+            return (core.time_group_stat(y, groups(y.device), stat=stat),)
+
+        (res,) = rec.walk(block, 0, plan.ngroups)
+        # (the groups lead wherever the input had tcoord: a leading dim with the plan's axis)
+        return rec.labeled(res, None, (tcoord,), {tcoord: plan.time})
+
+    return record.over(xobj, tcoord, one, plan.time, required=False)

@@ -15,10 +15,8 @@ tests/quantile_numpy.py restates it with ``numpy.sort``.  float64 results are va
 ``numpy.nanquantile(y[sel], q, axis=0)`` -- what xarray's ``.quantile(q, dim="time")`` gives -- up
 to the sign of a zero.
 
-Placement is the trend module's (``trend._Record``): a device tensor in gives a device tensor out
-and nothing crosses the host link; host arrays go up and come down through ``hostio``, a block of
-cells at a time when the record does not fit the device.  A cell's selection never leaves its lane,
-so the block size never changes a bit of the result.
+Placement is the record module's (``record.Record``): device in, device out; host arrays in blocks
+of cells.  A cell's selection never leaves its lane, so the block size never changes a bit.
 
 Dtypes: float32 records give float32 (selected and interpolated in float64, rounded once -- the
 convention of the grouped statistics, not numpy's float32 lerp); integer and boolean records are
@@ -28,9 +26,8 @@ computed and returned as float64; float16 and long double records are refused.  
 import numpy as np
 
 from .adapters import accepts_xarray
-from .climatology import _check_record_dtype
-from .filters import _over
 from .labeled import DataArray, Dataset
+from .record import Record, check_record_dtype, over, plan_groups
 
 __all__ = ["time_quantile", "time_median", "exceedance_count"]
 
@@ -58,43 +55,6 @@ def _plan(xobj, tcoord, by, time_axis_year=None):
     return climatology.yearly_plan(time_da, tcoord)
 
 
-class _Groups:
-    """a plan's lists, uploaded once per device"""
-
-    def __init__(self, plan, nt):
-        self.plan, self.nt, self.uploaded = plan, nt, {}
-
-    def on(self, device):
-        from . import core
-
-        if self.plan is None:
-            return None
-        if device not in self.uploaded:
-            self.uploaded[device] = core.upload_groups(self.plan.steps, self.plan.offsets, self.nt,
-                                                       device)
-        return self.uploaded[device]
-
-
-def _result(da, rec, data, tcoord, plan, lead_dims=(), lead_coords=None, attrs=None):
-    """``data`` (lead..., groups, cells...) as a DataArray: the group axis goes where the input had
-    ``tcoord`` (or leaves, without a plan: ``data`` is then (lead..., cells...)); the other dims keep
-    the input's order"""
-    nlead = len(lead_dims)
-    coords = {k: v for k, v in da.coords.items() if tcoord not in v.dims}
-    if plan is None:
-        dims = tuple(lead_dims) + rec.rest_dims
-    else:
-        dims = tuple(lead_dims) + tuple(da.dims)
-        if rec.axis:
-            data = (data.movedim(nlead, nlead + rec.axis) if hasattr(data, "movedim")
-                    else np.moveaxis(data, nlead, nlead + rec.axis))
-        coords[tcoord] = plan.time
-    coords.update(lead_coords or {})
-    out = DataArray(data, dims, coords, dict(da.attrs) if attrs is None else attrs, da.name)
-    out.encoding = dict(da.encoding)
-    return out
-
-
 # ---------------------------------------------------------------------------------------
 # public functions
 # ---------------------------------------------------------------------------------------
@@ -118,49 +78,27 @@ def time_quantile(xobj, q, tcoord="time", by=None, time_axis_year=None):
     levels = core.quantile_levels(q)
     scalar = np.ndim(q) == 0
     plan = _plan(xobj, tcoord, by, time_axis_year)
+    time = None if plan is None else plan.time  # (the plan's axis, or gone with the whole record)
+    qcoord = {"quantile": DataArray(np.float64(levels[0]) if scalar else levels.copy(),
+                                    () if scalar else ("quantile",), None, None, "quantile")}
 
     def one(da):
-        from .trend import _Record
+        check_record_dtype(da)
+        rec = Record(da, tcoord)
+        groups = plan_groups(plan, rec.nt)
 
-        _check_record_dtype(da)
-        rec = _Record(da, tcoord)
-        groups = _Groups(plan, rec.nt)
-
-        def block(y):
-            return (core.time_quantile(y, levels, groups.on(y.device)),)
+        def block(y, _cells):
+            return (core.time_quantile(y, levels, groups(y.device)),)
 
         (res,) = rec.walk(block, 0, levels.size * (1 if plan is None else plan.ngroups))
         # res: (nq, groups, cells...)
         if plan is None:
             res = res[:, 0]
-        qcoord = DataArray(np.float64(levels[0]) if scalar else levels.copy(),
-                           () if scalar else ("quantile",), None, None, "quantile")
         if scalar:
-            return _result(da, rec, res[0], tcoord, plan, (), {"quantile": qcoord})
-        return _result(da, rec, res, tcoord, plan, ("quantile",), {"quantile": qcoord})
+            return rec.labeled(res[0], time, (), qcoord)
+        return rec.labeled(res, time, ("quantile",), qcoord)
 
-    out = _over(xobj, tcoord, one)
-    return _regroup(out, xobj, tcoord, plan, scalar, levels)
-
-
-def _regroup(out, xobj, tcoord, plan, scalar=True, levels=None):
-    """a Dataset result's own coordinates: ``_over`` carried the input's; the time axis is the
-    plan's (or gone) and the quantile coordinate is new"""
-    if not isinstance(out, Dataset):
-        return out
-    result = Dataset()
-    for name, c in xobj.coords.items():
-        if tcoord not in c.dims:
-            result._set(name, c, is_coord=True)
-    if plan is not None:
-        result._set(tcoord, plan.time, is_coord=True)
-    if levels is not None:
-        result._set("quantile", DataArray(np.float64(levels[0]) if scalar else levels.copy(),
-                                          () if scalar else ("quantile",), None, None, "quantile"),
-                    is_coord=True)
-    for name, var in out.data_vars.items():
-        result[name] = var
-    return result
+    return over(xobj, tcoord, one, time, qcoord)
 
 
 @accepts_xarray
@@ -215,17 +153,16 @@ def exceedance_count(xobj, threshold, tcoord="time", by=None):
     from . import core
 
     plan = _plan(xobj, tcoord, by)
+    time = None if plan is None else plan.time
     if isinstance(threshold, Dataset) and not isinstance(xobj, Dataset):
         raise TypeError("a Dataset threshold needs a Dataset record")
     if not isinstance(threshold, (DataArray, Dataset)) and np.ndim(threshold) != 0:
         raise TypeError("threshold must be a number, a DataArray or a Dataset")
 
     def one(da):
-        from .trend import _Record
-
-        _check_record_dtype(da)
-        rec = _Record(da, tcoord)
-        groups = _Groups(plan, rec.nt)
+        check_record_dtype(da)
+        rec = Record(da, tcoord)
+        groups = plan_groups(plan, rec.nt)
         ngroups = 1 if plan is None else plan.ngroups
         thr = threshold
         if isinstance(thr, Dataset):
@@ -233,21 +170,14 @@ def exceedance_count(xobj, threshold, tcoord="time", by=None):
                 raise ValueError(f"the threshold dataset has no variable '{da.name}'")
             thr = thr[da.name]
         rows = _threshold_rows(thr, da, rec, tcoord, ngroups)
-        at = [0]  # (a host record is walked in consecutive blocks of cells)
 
-        def block(y):
-            c0, c1 = at[0], at[0] + y.shape[1]
-            at[0] = c1
-            part = rows[:, c0:c1]
+        def block(y, cells):
+            part = rows[:, cells]
             if not hasattr(part, "movedim"):
                 part = np.ascontiguousarray(part)
-            return (core.time_exceed_count(y, core._f64(part, y.device), groups.on(y.device)),)
+            return (core.time_exceed_count(y, core._f64(part, y.device), groups(y.device)),)
 
         (res,) = rec.walk(block, 0, 2 * ngroups)
-        if plan is None:
-            res = res[0]
-        coords = {}
-        return _result(da, rec, res, tcoord, plan, (), coords)
+        return rec.labeled(res[0] if plan is None else res, time)
 
-    out = _over(xobj, tcoord, one)
-    return _regroup(out, xobj, tcoord, plan)
+    return over(xobj, tcoord, one, time)

@@ -17,11 +17,9 @@ step is *valid* when it lies inside the record and is not NaN; invalid steps add
 weights.  The sum runs in float64 with k ascending, every output summed afresh
 (include/momlevel_filter.h states the contract, tests/filter_numpy.py restates it in numpy).
 
-Placement is the trend module's (``trend._Record``): a device tensor in gives a device tensor out
-and nothing crosses the host link; host arrays go up and come down through ``hostio``, a block of
-cells at a time when the record does not fit the device.  Each cell is filtered on its own, so the
-block size never changes a bit of the result.  The time axis and the order of the dims come back as
-they went in.
+Placement is the record module's (``record.Record``): device in, device out; host arrays in blocks
+of cells.  Each cell is filtered on its own, so the block size never changes a bit of the result.
+The time axis and the order of the dims come back as they went in.
 
 Dtypes: float32 records give float32 (the float64 result rounded once, the convention of the
 grouped statistics); everything else is computed and returned as float64.  ``rolling_trend`` always
@@ -32,8 +30,7 @@ import numpy as np
 
 from . import cftime_lite
 from .adapters import accepts_xarray
-from .climatology import _check_record_dtype, _is_numeric
-from .labeled import DataArray, Dataset
+from .record import Record, axis_values, check_record_dtype, over, per_device, slope_units
 
 __all__ = [
     "rolling_mean",
@@ -122,68 +119,34 @@ def trend_table(x, window, lead):
 # the record through the kernel
 # ---------------------------------------------------------------------------------------
 def _filter_array(da, tcoord, weights, lead, min_count, normalise, float64_out=False):
-    """one DataArray through ``core.time_filter``; ``weights``: (W,) or (nt, W), host float64"""
-    from . import core
-    from .trend import _Record
+    """one DataArray through ``core.time_filter``; ``weights``: (W,) or (nt, W), host float64 ->
+    ``(record, result (nt, cells...))``"""
+    import torch
 
-    _check_record_dtype(da)
-    rec = _Record(da, tcoord)
+    from . import core, hostio
+
+    check_record_dtype(da)
+    rec = Record(da, tcoord)
     weights = core.filter_weights(weights, rec.nt)
-    uploaded = {}
+    uploaded = per_device(lambda device: hostio.to_device(weights, device, torch.float64).contiguous())
 
-    def block(y):
-        import torch
-
-        from . import hostio
-
-        if y.device not in uploaded:
-            uploaded[y.device] = hostio.to_device(weights, y.device, torch.float64).contiguous()
-        return (core.time_filter(y, uploaded[y.device], lead, min_count, normalise,
+    def block(y, _cells):
+        return (core.time_filter(y, uploaded(y.device), lead, min_count, normalise,
                                  out_dtype=torch.float64 if float64_out else None),)
 
     (res,) = rec.walk(block, 1, 0)
-    return rec, rec.back(res)
-
-
-def _like_input(da, data, attrs=None, name=None):
-    out = DataArray(data, da.dims, da.coords, dict(da.attrs) if attrs is None else attrs,
-                    da.name if name is None else name)
-    out.encoding = dict(da.encoding)
-    return out
-
-
-def _over(xobj, tcoord, one):
-    """``one(DataArray)`` for a DataArray, or for every numeric variable of a Dataset that has
-    ``tcoord`` (as ``climatology.grouped_stat``: non-numeric variables are skipped, variables
-    without ``tcoord`` are left out; here every coordinate is kept, the time axis is unchanged)"""
-    if isinstance(xobj, DataArray):
-        if tcoord not in xobj.dims:
-            raise ValueError(f"the array has no dimension '{tcoord}'")
-        return one(xobj)
-    if isinstance(xobj, Dataset):
-        if not any(tcoord in v.dims for v in xobj.data_vars.values()):
-            raise ValueError(f"no variable of the dataset has a dimension '{tcoord}'")
-        result = Dataset()
-        for name, c in xobj.coords.items():
-            result._set(name, c, is_coord=True)
-        for name, var in xobj.data_vars.items():
-            if tcoord not in var.dims or not _is_numeric(var):
-                continue
-            res = one(xobj[name])  # (with the coordinates of its dims: rolling_trend reads the axis)
-            result[res.name if res.name is not None else name] = res
-        return result
-    raise TypeError("Input must be a DataArray or a Dataset")
+    return rec, res
 
 
 def _rolling(xobj, window, tcoord, center, min_periods, normalise):
     def one(da):
         w = _window(window, da.sizes[tcoord])
         mp = _min_periods(min_periods, w, w)
-        _rec, data = _filter_array(da, tcoord, np.ones(w), window_lead(w, center), mp, normalise)
-        return _like_input(da, data)
+        rec, data = _filter_array(da, tcoord, np.ones(w), window_lead(w, center), mp, normalise)
+        return rec.labeled(data)
 
     _min_periods(min_periods, _window(window), _window(window))  # (refused before any variable)
-    return _over(xobj, tcoord, one)
+    return over(xobj, tcoord, one)
 
 
 # ---------------------------------------------------------------------------------------
@@ -239,10 +202,10 @@ def time_filter(xobj, weights, tcoord="time", center=True, lead=None, skipna=Fal
 
     def one(da):
         _window(W, da.sizes[tcoord])
-        _rec, data = _filter_array(da, tcoord, w, int(lead), mp, bool(skipna))
-        return _like_input(da, data)
+        rec, data = _filter_array(da, tcoord, w, int(lead), mp, bool(skipna))
+        return rec.labeled(data)
 
-    return _over(xobj, tcoord, one)
+    return over(xobj, tcoord, one)
 
 
 @accepts_xarray
@@ -274,25 +237,19 @@ def rolling_trend(xobj, window, tcoord="time", time_units=None, center=True):
     (``trend_table``) and the kernel applies row t to the window of step t.  A window that leaves
     the record or holds a NaN step gives NaN: a NaN-skipping fit is not a fixed linear operator and
     is out of scope.  The result is float64 and named ``<name>_slope``; windows are placed as in
-    ``rolling_mean``.  For a calendar axis the slope is converted to ``time_units`` ("ns", "s",
-    "min", "hr", "day", "mon", "yr"; default "ns") and its ``units`` attribute is formed exactly as
-    in ``calc_linear_trend``."""
-    from .trend import _axis_values, time_conversion_factor
-
+    ``rolling_mean``.  For a calendar axis slope and ``units`` attribute are converted to
+    ``time_units`` by ``record.slope_units``, as in ``calc_linear_trend``."""
     def one(da):
         w = _window(window, da.sizes[tcoord])
         lead = window_lead(w, center)
-        axis = _axis_values(da, tcoord)
+        axis = axis_values(da, tcoord)
         table = trend_table(cftime_lite.axis_to_numeric(axis), w, lead)
-        _rec, slope = _filter_array(da, tcoord, table, lead, w, False, float64_out=True)
+        rec, slope = _filter_array(da, tcoord, table, lead, w, False, float64_out=True)
         attrs = dict(da.attrs)
         attrs["comment"] = f"Slope of linear trend over running windows of {w} steps"
         if cftime_lite.is_calendar_axis(axis):
-            units = "ns" if time_units is None else time_units
-            _units = attrs["units"] + " " if "units" in attrs.keys() else ""
-            _units = f"{_units} {units}-1"
-            slope = slope * (1.0 / time_conversion_factor("ns", units))
-            attrs["units"] = _units
-        return _like_input(da, slope, attrs, f"{da.name}_slope")
+            factor, attrs["units"] = slope_units(attrs, time_units)
+            slope = slope * factor
+        return rec.labeled(slope, attrs=attrs, name=f"{da.name}_slope")
 
-    return _over(xobj, tcoord, one)
+    return over(xobj, tcoord, one)

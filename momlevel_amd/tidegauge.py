@@ -18,7 +18,7 @@ BallTree leaves ties unspecified); the result does not depend on the launch geom
 
 Placement: a device record in gives device series out and nothing crosses the host link; a host (or
 lazily read) record goes up a block of rows at a time through ``hostio`` and the series come back
-as numpy arrays.  The record is laid out by ``trend._Record``, as for the fits and the grouped
+as numpy arrays.  The record is laid out by ``record.layout``, as for the fits and the grouped
 statistics.
 """
 
@@ -191,17 +191,16 @@ def _gather_series(arr, ydim, xdim, flat_index):
     """``(series (ng, nrest), rest_dims, rest_shape, on_device)``: the record with the horizontal
     dims last, flattened to (nrest, ny * nx) and gathered at ``flat_index`` in one launch (device
     record) or one launch per uploaded block of rows (host record)."""
-    from . import core, engine, hostio
-    from .trend import _Record
+    from . import core, engine, hostio, record
 
     rest_dims = tuple(d for d in arr.dims if d not in (ydim, xdim))
     moved = arr.transpose(*rest_dims, ydim, xdim)
     n = arr.sizes[ydim] * arr.sizes[xdim]
     rest_shape = tuple(arr.sizes[d] for d in rest_dims)
     nrest = int(np.prod(rest_shape, dtype=np.int64))
-    rec = _Record(moved, moved.dims[0])  # (contiguous, float32 kept, anything else float64)
-    y = rec.y.reshape(nrest, n)
-    if rec.device:
+    # (contiguous, float32 kept, anything else float64)
+    y = record.layout(moved, moved.dims[0]).reshape(nrest, n)
+    if moved.is_device:
         return core.gauge_gather(y, flat_index), rest_dims, rest_shape, True
     device = engine.device_of()
     index = torch_index(flat_index, device)

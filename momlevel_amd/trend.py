@@ -13,10 +13,8 @@ The reference fits through ``xarray.polyfit`` (numpy's lstsq, one CPU thread) an
 builds what depends on the time axis alone: its numeric values (``cftime_lite.axis_to_numeric``:
 what xarray's ``get_clean_interp_index`` yields), the 6-row model matrix and its pseudo-inverse.
 
-Placement: a device tensor in gives a device tensor out, nothing crosses the host link.  Host
-(or lazily read) arrays are uploaded and the results downloaded through ``hostio``'s staging,
-a block of cells at a time when record and result do not fit the device together: each cell's
-fit is independent, so the split never changes a bit of the result.
+Placement is the record module's (``record.Record``): device in, device out; host arrays in blocks
+of cells.  Each cell's fit is independent, so the split never changes a bit of the result.
 
 One documented deviation: a cell with fewer than 2 valid steps gets NaN for slope and intercept
 (numpy's lstsq returns a minimum-norm answer and a RankWarning there).
@@ -28,7 +26,8 @@ import numpy as np
 
 from . import cftime_lite
 from .adapters import accepts_xarray
-from .labeled import DataArray, Dataset, np_dtype
+from .labeled import DataArray, Dataset
+from .record import Record, axis_values, rest_coords, slope_units, to_end
 
 __all__ = [
     "broadcast_trend",
@@ -38,10 +37,6 @@ __all__ = [
     "seasonal_model",
     "deseason",
 ]
-
-# Cells per block when a host-resident record is walked in blocks; None = sized from free device
-# memory (engine.chunk_steps).  The result does not depend on it.
-BLOCK_CELLS = None
 
 COEFF_LABELS = ["constant", "trend", "sin_annual", "cos_annual", "sin_semiannual",
                 "cos_semiannual"]
@@ -69,15 +64,6 @@ def time_conversion_factor(src, dst, days_per_month=30.417, days_per_year=365.0)
 # ---------------------------------------------------------------------------------------
 # the time axis: everything that depends on it alone is made here, on the host
 # ---------------------------------------------------------------------------------------
-def _axis_values(arr, dim):
-    """the coordinate of ``dim`` (its objects / numbers), or 0..n-1 when there is none"""
-    if dim in arr.coords:
-        return np.asarray(arr.coords[dim].values)
-    if arr.dims == (dim,) and arr.name == dim:
-        return np.asarray(arr.values)
-    return np.arange(arr.sizes[dim], dtype=np.float64)
-
-
 def fit_axis(x):
     """``(xt, s, xmean)`` of a numeric axis: xt = (x - xmean) / s with xmean the mean over the
     whole axis and s = max|x - xmean| (1 if that is 0) -- the centred, scaled abscissa the fit
@@ -139,90 +125,6 @@ def deseason_decimal_year(time_values):
 
 
 # ---------------------------------------------------------------------------------------
-# the record: fit dimension first, every other axis flattened into cells
-# ---------------------------------------------------------------------------------------
-class _Record:
-    """``arr`` with ``dim`` moved to the front: a contiguous device tensor (device input: torch's
-    movedim().contiguous(), nothing leaves the device) or a host array to be walked in blocks."""
-
-    def __init__(self, arr, dim):
-        assert dim in arr.dims, f"Dimension {dim} not found in array"
-        self.axis = arr.dims.index(dim)
-        self.rest_dims = tuple(d for d in arr.dims if d != dim)
-        self.rest_shape = tuple(arr.sizes[d] for d in self.rest_dims)
-        self.nt = arr.sizes[dim]
-        self.n = int(np.prod(self.rest_shape, dtype=np.int64))
-        self.device = arr.is_device
-        if self.device:
-            import torch
-
-            y = arr.data.movedim(self.axis, 0)
-            if y.dtype not in (torch.float32, torch.float64):
-                y = y.to(torch.float64)
-            self.y = y.contiguous().reshape(self.nt, self.n)
-        else:
-            host = np.asarray(arr.transpose(dim, ...).values)
-            if np_dtype(host.dtype) != np.dtype(np.float32):
-                host = host.astype(np.float64, copy=False)
-            self.y = host.reshape(self.nt, self.n)
-
-    def walk(self, fn, step_outputs, cell_rows):
-        """Run ``fn(device block (nt, cells)) -> tuple of device tensors (..., cells)`` over the
-        record and return the outputs with the cells unflattened.  Device records: one call.  Host
-        records: a block of cells at a time through hostio, sized so that a block, its
-        ``step_outputs`` (nt, cells) results and ``cell_rows`` per-cell rows fit the device."""
-        if self.device:
-            return tuple(o.reshape(tuple(o.shape[:-1]) + self.rest_shape) for o in fn(self.y))
-        from . import engine, hostio
-
-        device = engine.device_of()
-        per_cell = self.nt * (self.y.dtype.itemsize + 8 * step_outputs) + 8 * cell_rows
-        block = BLOCK_CELLS or engine.chunk_steps(self.n, per_cell, device)
-        block = max(1, min(int(block), max(self.n, 1)))
-        outs = None
-        for c0 in range(0, self.n, block):
-            c1 = min(c0 + block, self.n)
-            res = fn(hostio.to_device(self.y[:, c0:c1], device))
-            if outs is None:
-                outs = [np.empty(tuple(r.shape[:-1]) + (self.n,), dtype=np_dtype(r.dtype))
-                        for r in res]  # (float64 for every fit; a grouped statistic keeps float32)
-            for o, r in zip(outs, res):
-                o[..., c0:c1] = hostio.to_host(r)
-        if outs is None:  # no cells at all
-            import torch
-
-            empty = torch.empty((self.nt, 0), dtype=torch.float64, device=device)
-            outs = [hostio.to_host(r) for r in fn(empty)]
-        return tuple(o.reshape(o.shape[:-1] + self.rest_shape) for o in outs)
-
-    def back(self, steps):
-        """a (nt, ...) result with the fit dimension back where the input had it (a view)"""
-        if self.axis == 0:
-            return steps
-        return steps.movedim(0, self.axis) if self.device else np.moveaxis(steps, 0, self.axis)
-
-
-def _to_end(steps):
-    """(nt, ...) -> (..., nt), a view: the dims of xarray's ``slope * index`` (trend.py:105)"""
-    if hasattr(steps, "movedim"):
-        return steps.movedim(0, -1)
-    return np.moveaxis(steps, 0, -1)
-
-
-def _rest_coords(arr, dims):
-    return {k: v for k, v in arr.coords.items() if set(v.dims) <= set(dims)}
-
-
-def _linfit_block(xt, s, xmean):
-    def fn(y):
-        from . import core
-
-        return core.time_linfit(y, xt, s, xmean)
-
-    return fn
-
-
-# ---------------------------------------------------------------------------------------
 # public functions
 # ---------------------------------------------------------------------------------------
 @accepts_xarray
@@ -276,7 +178,7 @@ def broadcast_trend(slope, dim_arr, subtract_time_zero=False):
     line = _apply_line(None, mode, x, data, None, slope.is_device)
     coords = dict(slope.coords)
     coords[dim_name] = DataArray(axis, (dim_name,), None, dim_arr.attrs, dim_name)
-    return DataArray(_to_end(line), slope.dims + (dim_name,), coords)
+    return DataArray(to_end(line), slope.dims + (dim_name,), coords)
 
 
 def _apply_line(y, mode, x, slope, intercept, on_device):
@@ -296,10 +198,16 @@ def _apply_line(y, mode, x, slope, intercept, on_device):
 
 def _fit(arr, dim):
     """(record, x, slope, intercept) of ``arr`` along ``dim``: slope per unit of the numeric axis"""
-    rec = _Record(arr, dim)
-    x = cftime_lite.axis_to_numeric(_axis_values(arr, dim))
+    rec = Record(arr, dim)
+    x = cftime_lite.axis_to_numeric(axis_values(arr, dim))
     xt, s, xmean = fit_axis(x)
-    slope, intercept = rec.walk(_linfit_block(xt, s, xmean), 0, 12)
+
+    def block(y, _cells):
+        from . import core
+
+        return core.time_linfit(y, xt, s, xmean)
+
+    slope, intercept = rec.walk(block, 0, 12)
     return rec, x, slope, intercept
 
 
@@ -317,23 +225,16 @@ def calc_linear_trend(arr, dim="time", time_units=None):
     assert isinstance(arr, DataArray), "`_detrend_array` only supports `xarray.DataArray` objects"
     varname = arr.name
     rec, _x, slope, intercept = _fit(arr, dim)
-    coords = _rest_coords(arr, rec.rest_dims)
+    coords = rest_coords(arr, rec.rest_dims)
 
     slope_attrs = dict(arr.attrs)
     slope_attrs["comment"] = "Slope of linear trend"
     intercept_attrs = dict(arr.attrs)
     intercept_attrs["comment"] = "Y-intercept of linear trend"
 
-    if cftime_lite.is_calendar_axis(_axis_values(arr, dim)):
-        time_units = "ns" if time_units is None else time_units
-        if "units" in slope_attrs.keys():
-            _units = slope_attrs["units"] + " "
-        else:
-            _units = ""
-        _units = f"{_units} {time_units}-1"
-        factor = 1.0 / time_conversion_factor("ns", time_units)
+    if cftime_lite.is_calendar_axis(axis_values(arr, dim)):
+        factor, slope_attrs["units"] = slope_units(slope_attrs, time_units)
         slope = slope * factor
-        slope_attrs["units"] = _units
 
     dsout = Dataset()
     dsout[f"{varname}_slope"] = DataArray(slope, rec.rest_dims, coords, slope_attrs,
@@ -353,18 +254,18 @@ def _detrend_array(arr, dim="time", order=1, mode="remove"):
     if mode not in ["remove", "correct"]:
         raise ValueError(f"Unknown detrend mode '{mode}'")
     varname = arr.name
-    rec = _Record(arr, dim)
-    x = cftime_lite.axis_to_numeric(_axis_values(arr, dim))
+    rec = Record(arr, dim)
+    x = cftime_lite.axis_to_numeric(axis_values(arr, dim))
     xt, s, xmean = fit_axis(x)
 
-    def block(y):
+    def block(y, _cells):
         from . import core
 
         m, b = core.time_linfit(y, xt, s, xmean)
         return m, b, core.time_apply(y, mode, x, m, b if mode == "remove" else None)
 
     slope, intercept, result = rec.walk(block, 1, 12)
-    coords = _rest_coords(arr, rec.rest_dims)
+    coords = rest_coords(arr, rec.rest_dims)
     slope = DataArray(slope, rec.rest_dims, coords, None, f"{varname}_slope")
     intercept = DataArray(intercept, rec.rest_dims, coords, None, f"{varname}_intercept")
     attrs = dict(arr.attrs)
@@ -409,7 +310,7 @@ def linear_detrend(xobj, dim="time", order=1, mode="remove"):
 def _project_apply(rec, model, pmodel, want):
     """coefficients (6, ...) and / or the model and residual records (nt, ...) of the K-term fit:
     mlx_time_project, then mlx_time_apply"""
-    def block(y):
+    def block(y, _cells):
         from . import core
 
         coef = core.time_project(y, pmodel)
@@ -437,9 +338,9 @@ def seasonal_model(da_timeseries, tcoord="time", return_model=False):
     ``dot`` leaves it.  ``standard_name`` / ``long_name`` / ``units`` as :433-458."""
     assert isinstance(da_timeseries, DataArray), "Input must be a DataArray"
     da_timeseries = da_timeseries.reset_coords(drop=True)
-    time_values = _axis_values(da_timeseries, tcoord)
+    time_values = axis_values(da_timeseries, tcoord)
     model, pmodel = seasonal_model_matrix(decimal_year(time_values))
-    rec = _Record(da_timeseries, tcoord)
+    rec = Record(da_timeseries, tcoord)
     smodel, residuals = _project_apply(rec, model, pmodel, ("model", "residuals"))
 
     attrs = da_timeseries.attrs
@@ -457,7 +358,7 @@ def seasonal_model(da_timeseries, tcoord="time", return_model=False):
         _long_name_r = "Seasonal residuals"
     _units = attrs["units"] if "units" in attrs.keys() else ""
 
-    smodel = DataArray(_to_end(smodel), rec.rest_dims + (tcoord,), da_timeseries.coords,
+    smodel = DataArray(to_end(smodel), rec.rest_dims + (tcoord,), da_timeseries.coords,
                        {"standard_name": _standard_name_m, "long_name": _long_name_m,
                         "units": _units})
     residuals = DataArray(rec.back(residuals), da_timeseries.dims, da_timeseries.coords,
@@ -487,12 +388,12 @@ def deseason(arr, tdim="time", output_format="residuals"):
     if output_format not in ("residuals", "model", "coeff"):
         raise ValueError(f"output_format {output_format} not recognized")
     attrs = dict(arr.attrs)
-    time_values = _axis_values(arr, "time" if "time" in arr.coords else tdim)  # (:776 arr.time)
+    time_values = axis_values(arr, "time" if "time" in arr.coords else tdim)  # (:776 arr.time)
     model, pmodel = seasonal_model_matrix(deseason_decimal_year(time_values))
-    rec = _Record(arr, tdim)
+    rec = Record(arr, tdim)
     (data,) = _project_apply(rec, model, pmodel, (output_format,))
 
-    coords = _rest_coords(arr, rec.rest_dims)
+    coords = rest_coords(arr, rec.rest_dims)
     if output_format == "coeff":
         dims = ("coeff",) + rec.rest_dims
         labels = np.empty(6, dtype=object)

@@ -20,7 +20,7 @@ import torch
 
 import clim_numpy as cn
 from conftest import assert_bit_equal
-from momlevel_amd import cftime_lite, climatology, core, test_data, trend, util
+from momlevel_amd import cftime_lite, climatology, core, record, test_data, util
 from momlevel_amd.labeled import DataArray, Dataset
 
 pytestmark = pytest.mark.gpu
@@ -177,11 +177,11 @@ def test_block_size_never_changes_a_bit(monkeypatch):
     y = _field((72, 9, 11), seed=8)
     da = DataArray(y, ("time", "lat", "lon"), {"time": time}, None, "v")
     for func in STATS:
-        monkeypatch.setattr(trend, "BLOCK_CELLS", None)
+        monkeypatch.setattr(record, "BLOCK_CELLS", None)
         whole = util.annual_cycle(da, func=func).values
         _bits(whole, cn.annual_cycle(y, time.values, func), f"one block, {func}")
         for block in (1, 7, 32):  # 99 cells: blocks of odd and even width, a ragged last block
-            monkeypatch.setattr(trend, "BLOCK_CELLS", block)
+            monkeypatch.setattr(record, "BLOCK_CELLS", block)
             _bits(util.annual_cycle(da, func=func).values, whole, f"blocks of {block} cells, {func}")
 
 

@@ -9,7 +9,7 @@ import torch
 
 import filter_numpy as fn
 from conftest import assert_bit_equal
-from momlevel_amd import cftime_lite, filters, trend
+from momlevel_amd import cftime_lite, filters, record, trend
 from momlevel_amd.labeled import DataArray, Dataset
 
 pytestmark = pytest.mark.gpu
@@ -110,7 +110,7 @@ def test_host_record_walked_in_blocks(monkeypatch):
     y = _field((36, 5, 6), seed=2)
     da = DataArray(y, ("time", "lat", "lon"), {"time": _monthly_axis(3)}, None, "eta")
     whole = _np(filters.rolling_mean(da, 5, min_periods=2))
-    monkeypatch.setattr(trend, "BLOCK_CELLS", 7)
+    monkeypatch.setattr(record, "BLOCK_CELLS", 7)
     assert_bit_equal(_np(filters.rolling_mean(da, 5, min_periods=2)), whole, "blocks of 7 cells")
 
 

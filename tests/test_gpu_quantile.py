@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import quantile_numpy as qn
-from momlevel_amd import climatology, extremes, trend
+from momlevel_amd import climatology, extremes, record
 from momlevel_amd.cftime_lite import daily_midpoints
 from momlevel_amd.labeled import DataArray, Dataset
 
@@ -58,7 +58,7 @@ def test_host_and_device_records_agree_bit_for_bit(dtype, monkeypatch):
     q = [0.05, 0.5, 0.95]
     dev = extremes.time_quantile(_record(dtype, device=True), q)
     assert dev.is_device and dev.data.is_cuda and dev.dims == ("quantile", "yh", "xh")
-    monkeypatch.setattr(trend, "BLOCK_CELLS", 7)  # the host record goes up in five blocks of cells
+    monkeypatch.setattr(record, "BLOCK_CELLS", 7)  # the host record goes up in five blocks of cells
     host = extremes.time_quantile(_record(dtype), q)
     assert not host.is_device and host.dtype == dtype and host.shape == (3, NY, NX)
     assert _host(dev).tobytes() == host.values.tobytes()
@@ -71,6 +71,30 @@ def test_host_and_device_records_agree_bit_for_bit(dtype, monkeypatch):
     y = _values(dtype).reshape(NT, -1)
     assert np.array_equal(cnt_host.values.reshape(1, -1),
                           qn.exceed_count(y, host.values[1].reshape(1, -1)))
+
+
+def test_blocked_host_exceedance_slices_a_per_cell_threshold(monkeypatch):
+    """A host float32 record (yh 5, time 24, xh 7) goes up in five blocks of 7 cells against a
+    threshold that differs in every cell, with a NaN cell: every block must meet its own slice of
+    the threshold.  Exactly the single-call device result and the numpy restatement (int64)."""
+    rng = np.random.default_rng(33)
+    y = rng.normal(0.0, 1.0, (5, 24, 7)).astype(np.float32)
+    y[2, :, 3] = np.nan
+    thr = rng.normal(0.0, 0.5, (5, 7))
+    flat = np.moveaxis(y, 1, 0).reshape(24, 35)
+    want = qn.exceed_count(flat, thr.reshape(1, 35)).reshape(5, 7)
+    # (the check has teeth: the first block's thresholds for every block give other counts)
+    assert not np.array_equal(want, qn.exceed_count(flat, np.tile(thr[0], 5)[None]).reshape(5, 7))
+    monkeypatch.setattr(record, "BLOCK_CELLS", 7)
+    dev = extremes.exceedance_count(
+        DataArray(torch.from_numpy(y).to(DEV), ("yh", "time", "xh"), None, None, "zos"),
+        DataArray(thr, ("yh", "xh")))
+    host = extremes.exceedance_count(DataArray(y, ("yh", "time", "xh"), None, None, "zos"),
+                                     DataArray(thr, ("yh", "xh")))
+    assert dev.is_device and dev.data.dtype == torch.int64 and dev.dims == ("yh", "xh")
+    assert not host.is_device and host.dtype == np.int64 and host.dims == ("yh", "xh")
+    assert np.array_equal(host.values, want) and np.array_equal(_host(dev), want)
+    assert want[2, 3] == 0
 
 
 def test_scalar_against_sequence_layout_and_the_median():

@@ -341,7 +341,7 @@ def test_gather_is_bit_equal_to_fancy_indexing(lead, dtype):
     # host input gives a host result
     check(tidegauge.extract_tidegauge(DataArray(host, dims), geolon, geolat, csv=table,
                                       mask=DataArray(mask, ("yh", "xh"))), False)
-    # a transposed, non-contiguous record (device and host): laid out by trend._Record
+    # a transposed, non-contiguous record (device and host): laid out by record.layout
     order = ("xh",) + dims[:-2] + ("yh",)
     perm = [dims.index(d) for d in order]
     turned = DataArray(torch.from_numpy(host).cuda().permute(*perm), order)

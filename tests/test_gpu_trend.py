@@ -25,7 +25,7 @@ import torch
 
 import trend_numpy as tn
 from conftest import assert_bit_equal
-from momlevel_amd import cftime_lite, steric, test_data, trend, util
+from momlevel_amd import cftime_lite, record, steric, test_data, trend, util
 from momlevel_amd.labeled import DataArray, Dataset
 
 pytestmark = pytest.mark.gpu
@@ -299,7 +299,7 @@ def test_results_are_deterministic_and_independent_of_the_cell_blocks(monkeypatc
         for g, w in zip(again, base):
             assert_bit_equal(g, w, what)
     for block in (1, 7, 32, 50):  # blocks of cells that change the pack width and leave a tail
-        monkeypatch.setattr(trend, "BLOCK_CELLS", block)
+        monkeypatch.setattr(record, "BLOCK_CELLS", block)
         for g, w in zip(everything(arr), base):
             assert_bit_equal(g, w, f"blocks of {block} cells")
 

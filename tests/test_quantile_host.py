@@ -137,7 +137,7 @@ def test_yearly_plan_takes_ragged_and_unordered_years():
 def stubbed(monkeypatch):
     """core.time_quantile / time_exceed_count answered by the restatement on CPU tensors, host
     records walked in blocks of 7 cells without a device"""
-    from momlevel_amd import engine, hostio, trend
+    from momlevel_amd import engine, hostio, record
 
     calls = []
 
@@ -154,7 +154,7 @@ def stubbed(monkeypatch):
 
     monkeypatch.setattr(core, "time_quantile", time_quantile)
     monkeypatch.setattr(core, "time_exceed_count", time_exceed_count)
-    monkeypatch.setattr(trend, "BLOCK_CELLS", 7)
+    monkeypatch.setattr(record, "BLOCK_CELLS", 7)
     monkeypatch.setattr(engine, "device_of", lambda *a, **k: torch.device("cpu"))
     monkeypatch.setattr(hostio, "to_device", lambda x, device, dtype=None: torch.from_numpy(
         np.ascontiguousarray(x)) if dtype is None else torch.from_numpy(
