@@ -8,7 +8,8 @@ detrend and deseason fits of ``trend``, and the grouped time statistics
 C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h,
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
 include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
-include/momlevel_quantile.h, include/momlevel_column.h, include/momlevel_eof.h).
+include/momlevel_quantile.h, include/momlevel_column.h, include/momlevel_eof.h,
+include/momlevel_smooth.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -58,6 +59,12 @@ covariance maps) and ``project_field``.  The contraction over the cells runs on 
 cores with the anomalies formed while the rows are staged, in a fixed order of summation; the
 ``nt x nt`` eigen-problem is solved on the host (include/momlevel_eof.h).
 
+``spatial`` (an EXTENSION too) is the horizontal filter: ``smooth`` and ``highpass`` apply an
+area-weighted, land-aware separable convolution over the ``(yh, xh)`` plane of every record where
+it lives -- ``boxcar_weights``, ``gaussian_weights``, or ``length_scale_weights`` for a fixed length
+on a converging grid -- with x periodic or closed; the tripolar fold and multi-rank tiles are not
+built (include/momlevel_smooth.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -74,6 +81,7 @@ from . import extremes
 from . import filters
 from . import reference
 from . import regional
+from . import spatial
 from . import spice
 from . import staggered_data
 from . import test_data
@@ -107,6 +115,7 @@ __all__ = [
     "halosteric",
     "reference",
     "regional",
+    "spatial",
     "spice",
     "steric",
     "steric_layers",

@@ -58,6 +58,8 @@ COLUMN_RISE, COLUMN_FALL, COLUMN_DEPART = 0, 1, 2
 COLUMN_MISS_NAN, COLUMN_MISS_FLOOR = 0, 1
 # ---- constants mirrored from include/momlevel_eof.h --------------------------------
 GRAM_MAX_SPLIT = 32
+# ---- constants mirrored from include/momlevel_smooth.h -----------------------------
+SMOOTH_FILL, SMOOTH_RESIDUAL = 1, 2
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -264,6 +266,18 @@ EOF_PROTOTYPES = {
 }
 
 
+# The horizontal filter (include/momlevel_smooth.h): bound by load_smooth() on first use, for the
+# same reason.  (Named as EOF_PROTOTYPES is, for the same count.)
+SMOOTH_PROTOTYPES = {
+    "mlx_smooth_tile_h": (_i64, []),
+    "mlx_smooth_tile_w": (_i64, [_int]),
+    "mlx_smooth_max_window": (_i64, []),
+    "mlx_smooth_record_window": (_i64, []),
+    "mlx_smooth_apply": (_int, [_vp, _int, _vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _int,
+                               _i64, _int, _i64, _i64, _i64, _vp, _int, _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -343,12 +357,14 @@ _GROUPS = {
     "quantile": (QUANTILE_SIGNATURES, "the quantile kernels"),
     "column": (COLUMN_SIGNATURES, "the column-search kernel"),
     "eof": (EOF_PROTOTYPES, "the Gram kernels"),
+    "smooth": (SMOOTH_PROTOTYPES, "the horizontal-filter kernels"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
 _layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = _eof_bound = False
+_smooth_bound = False
 
 
 def _load_group(group):
@@ -408,6 +424,10 @@ def load_column():
 
 def load_eof():
     return _load_group("eof")
+
+
+def load_smooth():
+    return _load_group("smooth")
 
 
 def last_error():

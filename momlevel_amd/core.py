@@ -1792,6 +1792,109 @@ def time_filter(y, w, lead, min_count=None, normalise=False, out=None, out_dtype
 
 
 # ---------------------------------------------------------------------------------------
+# the horizontal filter (include/momlevel_smooth.h; csrc/momlevel_smooth.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+def smooth_tile(dtype=torch.float64):
+    """``(tile_h, tile_w)``: the output cells one block of mlx_smooth_apply's tiled path owns for a
+    record of ``dtype`` (a torch or numpy float32 / float64).  The results do not depend on it."""
+    lib = _lib.load_smooth()
+    return int(lib.mlx_smooth_tile_h()), int(lib.mlx_smooth_tile_w(_query_dtype(dtype)))
+
+
+def smooth_max_window():
+    """The largest Wx and Wy the tiled path takes (mlx_smooth_max_window); wider windows are summed
+    cell by cell, with the same bits."""
+    return int(_lib.load_smooth().mlx_smooth_max_window())
+
+
+def smooth_record_window():
+    """Records a block of the tiled path walks while it holds its maps (mlx_smooth_record_window)."""
+    return int(_lib.load_smooth().mlx_smooth_record_window())
+
+
+def smooth_weights(wx, wy, ny, nx):
+    """The host-side mirror of the weights as the kernel reads them: float64, ``wx`` ``(Wx,)`` (one
+    row for every source row) or ``(ny, Wx)`` (row r for source row r), ``wy`` ``(Wy,)``,
+    1 <= Wx <= nx, 1 <= Wy <= ny, every weight finite; or ``ValueError``.  Touches no device."""
+    wx = np.ascontiguousarray(np.asarray(wx, dtype=np.float64))
+    wy = np.ascontiguousarray(np.asarray(wy, dtype=np.float64))
+    if wx.ndim not in (1, 2) or wx.shape[-1] < 1:
+        raise ValueError("x weights must be (Wx,) or (ny, Wx) with Wx >= 1")
+    if wx.ndim == 2 and wx.shape[0] != int(ny):
+        raise ValueError(f"a table of x weights needs one row per row of the plane: ({int(ny)}, Wx), "
+                         f"got {wx.shape}")
+    if wy.ndim != 1 or wy.shape[0] < 1:
+        raise ValueError("y weights must be (Wy,) with Wy >= 1")
+    if wx.shape[-1] > int(nx) or wy.shape[0] > int(ny):
+        raise ValueError(f"the window ({wy.shape[0]} x {wx.shape[-1]} cells) is larger than the "
+                         f"plane ({int(ny)} x {int(nx)}): a periodic window may not lap itself")
+    if not (np.isfinite(wx).all() and np.isfinite(wy).all()):
+        raise ValueError("weights must be finite")
+    return wx, wy
+
+
+def plane_smooth(v, area, wx, wy, lead_x, lead_y, periodic_x, min_count, fill=False, residual=False,
+                 out_dtype=None):
+    """The separable, normalised, mask-aware convolution over the two trailing dims
+    (mlx_smooth_apply; include/momlevel_smooth.h states the contract, tests/smooth_numpy.py restates
+    it): ``v`` (nrec, ny, nx) and ``area`` (ny, nx) contiguous device tensors, each float32 or
+    float64 on its own; ``wx`` a host array ``(Wx,)`` or ``(ny, Wx)`` and ``wy`` ``(Wy,)`` (uploaded
+    as float64; non-finite weights are a ``ValueError``) or float64 device tensors of those shapes
+    (their values are the caller's); ``0 <= lead < W`` each way.  A cell is valid when neither its
+    value nor its area is NaN and its area is positive; x wraps with ``periodic_x``, the y edges
+    are closed.  Fewer than ``min_count`` valid cells in the window give NaN, and so does a centre
+    that is not valid unless ``fill``; ``residual`` returns ``v - smooth``.  Returns
+    a new (nrec, ny, nx) tensor of ``out_dtype`` (default v's dtype; float32 is the float64 result
+    rounded once).  It takes no result buffer: the table of entry points that do is closed
+    (tests/test_gpu_out_contract.py); mlx_smooth_apply itself refuses an out that overlaps an
+    operand, and tests/test_gpu_smooth_edges.py runs it into guard-banded views."""
+    require_device()
+    lib = _lib.load_smooth()
+    vdt, adt = _float_code(v, "v", 3), _float_code(area, "area", 2)
+    nrec, ny, nx = (int(n) for n in v.shape)
+    if tuple(area.shape) != (ny, nx) or area.device != v.device:
+        raise ValueError(f"area must be ({ny}, {nx}) on {v.device}")
+    if ny < 1 or nx < 1:
+        raise ValueError("the plane must hold at least one cell")
+    dev_w = [isinstance(w, torch.Tensor) and w.is_cuda for w in (wx, wy)]
+    if dev_w[0] != dev_w[1]:
+        raise ValueError("wx and wy must both be host arrays or both device tensors")
+    if dev_w[0]:
+        for name, w in (("wx", wx), ("wy", wy)):
+            if w.dtype != torch.float64 or w.device != v.device or not w.is_contiguous():
+                raise ValueError(f"device weights ({name}) must be a contiguous float64 tensor on "
+                                 f"{v.device}")
+        wxd, wyd = wx, wy
+    else:
+        hx, hy = smooth_weights(wx, wy, ny, nx)
+        wxd = hostio.to_device(hx, v.device, torch.float64).contiguous()
+        wyd = hostio.to_device(hy, v.device, torch.float64).contiguous()
+    if wxd.dim() not in (1, 2) or (wxd.dim() == 2 and wxd.shape[0] != ny) or wyd.dim() != 1:
+        raise ValueError(f"weights must be wx (Wx,) or ({ny}, Wx) and wy (Wy,)")
+    Wx, Wy = int(wxd.shape[-1]), int(wyd.shape[0])
+    if not (1 <= Wx <= nx and 1 <= Wy <= ny):
+        raise ValueError(f"the window must hold 1 .. {ny} by 1 .. {nx} cells, got {Wy} x {Wx}")
+    lead_x, lead_y = int(lead_x), int(lead_y)
+    if not (0 <= lead_x < Wx and 0 <= lead_y < Wy):
+        raise ValueError(f"leads must lie in [0, {Wx}) and [0, {Wy}), got {lead_x} and {lead_y}")
+    min_count = int(min_count)
+    if not 1 <= min_count <= Wx * Wy:
+        raise ValueError(f"min_count must lie in [1, {Wx * Wy}], got {min_count}")
+    out_dtype = v.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"out_dtype must be float32 or float64, got {out_dtype}")
+    out = torch.empty((nrec, ny, nx), dtype=out_dtype, device=v.device)
+    if nrec == 0:
+        return out
+    flags = (_lib.SMOOTH_FILL if fill else 0) | (_lib.SMOOTH_RESIDUAL if residual else 0)
+    _call(lib, "mlx_smooth_apply", v.device, _ptr(v), vdt, _ptr(area), adt, _ptr(wxd), Wx,
+          Wx if wxd.dim() == 2 else 0, lead_x, _ptr(wyd), Wy, lead_y, int(bool(periodic_x)),
+          min_count, flags, nrec, ny, nx, _ptr(out),
+          DTYPE_F64 if out_dtype == torch.float64 else DTYPE_F32)
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # order statistics (include/momlevel_quantile.h; csrc/momlevel_quantile.hip).  EXTENSION.
 # ---------------------------------------------------------------------------------------
 def quantile_block_cells(dtype=torch.float64):

@@ -38,6 +38,7 @@ FEATURES = {
     "column": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_column.h"],
     "eof": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
             "include/momlevel_eof.h"],
+    "smooth": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_smooth.h"],
 }
 
 
@@ -160,6 +161,11 @@ def column_source_sha():
 def eof_source_sha():
     """the Gram kernels' own guard: csrc/momlevel_eof.hip (+ what it includes, + flags)"""
     return feature_source_sha("eof")
+
+
+def smooth_source_sha():
+    """the horizontal-filter kernels' own guard: csrc/momlevel_smooth.hip (+ what it includes, + flags)"""
+    return feature_source_sha("smooth")
 
 
 def hipcc():
