@@ -283,3 +283,106 @@ def test_located_grid_positions():
     flat = tidegauge.Located(np.array([0]), np.array([1.0]), np.array([7]), (300,), np.array([5]),
                              (np.zeros(1), np.zeros(1)), np.array([7]), np.array([1.0]))
     assert flat.iy.tolist() == [0] and flat.ix.tolist() == [7]
+
+
+# ---- the helpers of tests/test_gpu_tidegauge_edges.py ---------------------------------------------
+LATTICE_NS = (1, 255, 256, 257, 511, 513, 1024, 1025, 2337, 40 * 64)
+
+
+@pytest.mark.parametrize("edges_valid", (True, False))
+@pytest.mark.parametrize("kind", ("U", "D"))
+def test_lattice_helper_agrees_with_a_float64_argmin(kind, edges_valid):
+    for n in LATTICE_NS:
+        pq, pok = gn.lattice_points(n, kind, edges_valid)
+        gq, gok = gn.lattice_gauges(n, kind)
+        assert np.array_equal(np.sort(pq // 4), np.arange(n) if kind == "U" else np.arange(n) // 2)
+        edges = [i for i in gn.LATTICE_EDGES + (n - 1,) if i < n]
+        assert np.all(pok[edges] == edges_valid) and int((~gok).sum()) == 3
+        if n >= 255:
+            assert 0.03 * n < (~pok).sum() < 0.2 * n
+        points, gauges = gn.lattice_table(pq, pok), gn.lattice_table(gq, gok)
+        assert points.shape == (5, n) and gauges.shape == (5, gq.size)
+        bad = points[:, ~pok]
+        assert np.all(bad[:3] == np.inf) and np.isnan(bad[3:]).all() and not points[1:, pok].any()
+        want = gn.lattice_nearest(pq, pok, gq, gok)
+        # float64, as the search computes it: the squared chord, numpy's first minimum
+        with np.errstate(invalid="ignore"):
+            d = (gauges[0][:, None] - points[0][None, :]) ** 2
+        d[:, ~pok] = np.inf
+        got = np.where(gok & pok.any(), np.argmin(np.where(np.isnan(d), np.inf, d), axis=1), -1)
+        assert np.array_equal(got, want), (n, kind)
+        assert np.all(pok[want[want >= 0]]) and np.array_equal(want < 0, ~gok | ~pok.any())
+        if kind == "U":  # every valid point is the winner of the gauge on its own value
+            assert np.array_equal(np.unique(want[want >= 0]), np.nonzero(pok)[0])
+            mine = np.nonzero(pok)[0]
+            assert np.array_equal(want[gok][pq[mine] // 4], mine)
+        else:  # v + 0.5 ties across two values, v and v + 0.25 across the two copies of one
+            tied = (d == d.min(axis=1)[:, None]).sum(axis=1)
+            assert n < 255 or (tied[gok] == 4).any() and (tied[gok] == 2).any()
+
+
+def test_stacked_rows_and_their_expected_winners():
+    for copies in (20, 40):
+        lat, lon, mask, wet = gn.stacked_rows(copies)
+        m = 70
+        assert lat.shape == lon.shape == mask.shape == (copies, m) and len(wet) == m
+        assert np.array_equal(lat, np.tile(lat[0], (copies, 1))) and len(set(lat[0])) == m
+        sets = set(wet)
+        assert set(gn.TIE_SETS) <= sets and (copies - 1,) in sets and () in sets
+        assert (set(gn.TIE_SETS_40) <= sets) == (copies == 40)
+        assert wet.count(()) == 1 and wet[gn.TIE_DRY_COLUMN] == ()
+        for c, s in enumerate(wet):
+            assert np.array_equal(np.nonzero(mask[:, c])[0], sorted(s))
+        # a candidate of a later part meets one of an earlier part in a lower lane of the 16
+        assert any(max(s) >= 16 and min(s) % 16 > max(s) % 16 for s in sets if s)
+        for dlat, dlon in ((0.0, 0.0), (0.01, -0.01)):
+            index, _angle, _gap = gn.nearest(lat, lon, lat[0] + dlat, lon[0] + dlon, mask)
+            direct = np.array([min(s) * m + c if s else -1 for c, s in enumerate(wet)])
+            assert np.array_equal(index[direct >= 0], direct[direct >= 0])
+            dry = gn.TIE_DRY_COLUMN
+            assert index[dry] % m in (dry - 1, dry + 1) and index[dry] // m == min(wet[index[dry] % m])
+            one_row = (mask.sum(axis=0) > 0).astype(np.float64)
+            _i, _a, gap = gn.nearest(lat[0], lon[0], lat[0, dry] + dlat, lon[0, dry] + dlon, one_row)
+            assert gap[0] >= 1e-9
+
+
+def test_the_real_coordinate_cases_exclude_no_gauge():
+    lat, lon, mask, _glat, _glon = gn.synthetic_grid(41, 57, 1, 11)
+    dry = mask.reshape(-1) == 0.0
+    assert lat.size == 2337 and int(dry.sum()) == 709
+    index, angle, gap = gn.nearest(lat, lon, lat, lon, mask)
+    assert np.array_equal(index[~dry], np.nonzero(~dry)[0]) and np.all(angle[~dry] == 0.0)
+    assert not np.any(index[dry] == np.nonzero(dry)[0])
+    print("41x57, dry gauges: smallest relative gap", gap[dry].min())
+    assert gap.min() >= 1e-9 and 1.2e-4 < gap[dry].min() < 1.3e-4
+    lat2, _lon2, mask2, glat, glon = gn.synthetic_grid(41, 57, 513, 11)
+    assert np.array_equal(lat2, lat) and np.array_equal(mask2, mask)  # the gauges are drawn last
+    _i, _a, gap = gn.nearest(lat, lon, glat, glon, mask)
+    print("41x57, 513 gauges: smallest relative gap", gap.min())
+    assert gap.min() >= 1e-9
+    lib = _lib.load_gauge()
+    for ny, nx in ((257, 510), (257, 511)):
+        lat, lon, mask, glat, glon = gn.synthetic_grid(ny, nx, 5, 5)
+        _i, _a, gap = gn.nearest(lat, lon, glat, glon, mask)
+        print(f"{ny}x{nx}, 5 gauges: smallest relative gap", gap.min())
+        assert gap.min() >= 1e-9
+        n = ny * nx
+        assert 16 < lib.mlx_gauge_nearest_split(n, 5, n) <= 65535
+        assert 16 < lib.mlx_gauge_nearest_split(n, 5, 0) <= 65535
+    assert lib.mlx_gauge_nearest_split(131070, 5, 131070) == 65535
+    assert lib.mlx_gauge_nearest_split(131070, 5, 65536) == 65535
+
+
+def test_antipodes_round_above_one_in_numpy():
+    lat, lon, glat, glon = gn.antipodes(0.25)
+    assert lat.size == 721 and lat[0] == -90.0 and lat[360] == 0.0 and lat[-1] == 90.0
+    assert np.array_equal(glat, -lat) and np.all(glon - lon == 180.0)
+    args = np.deg2rad([glat, glon, lat, lon])
+    h = gn.haversine_h(*args)
+    print("h > 1 at", int((h > 1.0).sum()), "of 721; largest h - 1:", float(h.max() - 1.0))
+    assert (h > 1.0).sum() >= 3
+    with np.errstate(invalid="ignore"):
+        angle = gn.haversine(*args)
+    short = np.pi - angle[~np.isnan(angle)]
+    print("numpy's own pi - angle reaches", float(short.max()))
+    assert short.max() <= 2.0 * np.sqrt(2.0 * 16 * 2.0 ** -53)  # the GPU test's bound holds for numpy
