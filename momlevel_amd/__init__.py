@@ -9,7 +9,7 @@ C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
 include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
 include/momlevel_quantile.h, include/momlevel_column.h, include/momlevel_eof.h,
-include/momlevel_smooth.h).
+include/momlevel_smooth.h, include/momlevel_regrid.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -65,6 +65,14 @@ it lives -- ``boxcar_weights``, ``gaussian_weights``, or ``length_scale_weights`
 on a converging grid -- with x periodic or closed; the tripolar fold and multi-rank tiles are not
 built (include/momlevel_smooth.h).
 
+``regrid`` (an EXTENSION too) moves a ``(..., yh, xh)`` record to another grid where it lives: a
+gather through a sparse weight table with the weights of the sources present renormalised --
+``coarsen_weights`` (conservative blocks of any grid), ``conservative_weights`` (rectilinear
+lat/lon grids), ``nearest_weights`` or any ESMF-style table through ``from_triplets``, then
+``apply`` or the one-call ``coarsen``.  Bilinear and curvilinear conservative weights are not
+generated, the tripolar fold is not part of the coarsening's periodic option and a table is not
+spread over ranks (include/momlevel_regrid.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -81,6 +89,7 @@ from . import extremes
 from . import filters
 from . import reference
 from . import regional
+from . import regrid
 from . import spatial
 from . import spice
 from . import staggered_data
@@ -115,6 +124,7 @@ __all__ = [
     "halosteric",
     "reference",
     "regional",
+    "regrid",
     "spatial",
     "spice",
     "steric",

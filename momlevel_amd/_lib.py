@@ -60,6 +60,8 @@ COLUMN_MISS_NAN, COLUMN_MISS_FLOOR = 0, 1
 GRAM_MAX_SPLIT = 32
 # ---- constants mirrored from include/momlevel_smooth.h -----------------------------
 SMOOTH_FILL, SMOOTH_RESIDUAL = 1, 2
+# ---- constants mirrored from include/momlevel_regrid.h -----------------------------
+REGRID_PROPAGATE, REGRID_NO_RENORM = 1, 2
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -278,6 +280,16 @@ SMOOTH_PROTOTYPES = {
 }
 
 
+# The grid-to-grid remap (include/momlevel_regrid.h): bound by load_regrid() on first use, for the
+# same reason.  (Named as EOF_PROTOTYPES is, for the same count.)
+REGRID_PROTOTYPES = {
+    "mlx_regrid_slice": (_i64, []),
+    "mlx_regrid_record_window": (_i64, []),
+    "mlx_regrid_apply": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _dbl, _int, _i64, _i64, _i64,
+                               _vp, _int, _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -358,13 +370,14 @@ _GROUPS = {
     "column": (COLUMN_SIGNATURES, "the column-search kernel"),
     "eof": (EOF_PROTOTYPES, "the Gram kernels"),
     "smooth": (SMOOTH_PROTOTYPES, "the horizontal-filter kernels"),
+    "regrid": (REGRID_PROTOTYPES, "the remap kernel"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
 _layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = _eof_bound = False
-_smooth_bound = False
+_smooth_bound = _regrid_bound = False
 
 
 def _load_group(group):
@@ -428,6 +441,10 @@ def load_eof():
 
 def load_smooth():
     return _load_group("smooth")
+
+
+def load_regrid():
+    return _load_group("regrid")
 
 
 def last_error():

@@ -1895,6 +1895,72 @@ def plane_smooth(v, area, wx, wy, lead_x, lead_y, periodic_x, min_count, fill=Fa
 
 
 # ---------------------------------------------------------------------------------------
+# the grid-to-grid remap (include/momlevel_regrid.h; csrc/momlevel_regrid.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+def regrid_slice():
+    """Destinations of one slice of the remap table (mlx_regrid_slice): one wave owns a slice, one
+    lane a destination.  The results do not depend on it; the packed layout does."""
+    return int(_lib.load_regrid().mlx_regrid_slice())
+
+
+def regrid_record_window():
+    """Records a block walks on one read of its table entries (mlx_regrid_record_window)."""
+    return int(_lib.load_regrid().mlx_regrid_record_window())
+
+
+def regrid_apply(v, plan_tensors, nsrc, ndst, min_frac=0.0, propagate=False, renorm=True,
+                 out_dtype=None):
+    """The remap through a sparse weight table (mlx_regrid_apply; include/momlevel_regrid.h states
+    the contract and the packed layout, tests/regrid_numpy.py restates both): ``v`` (nrec, nsrc) a
+    contiguous float32 or float64 device tensor; ``plan_tensors`` = ``(slice_ptr, len, col, S)``,
+    contiguous 1-D device tensors on v's device -- int64 ``(ceil(ndst / regrid_slice()) + 1,)``,
+    int32 ``(ndst,)``, int32 ``(nentries,)`` and float64 ``(nentries,)`` (their values are the
+    caller's: whatever they hold, the kernel reads nothing outside them).  Sources that are NaN are
+    left out and the weights present renormalised (``renorm=False``: not renormalised); a
+    destination whose valid weight is below ``min_frac`` of its whole weight, or without a valid
+    source, is NaN; ``propagate`` makes any NaN source a NaN result instead.  Returns a new
+    (nrec, ndst) tensor of ``out_dtype`` (default v's dtype; float32 is the float64 result rounded
+    once).  It takes no result buffer: the table of entry points that do is closed
+    (tests/test_gpu_out_contract.py); mlx_regrid_apply itself refuses an out that overlaps an
+    operand, and tests/test_gpu_regrid_edges.py runs it into guard-banded views."""
+    require_device()
+    lib = _lib.load_regrid()
+    vdt = _float_code(v, "v", 2)
+    nrec, nsrc, ndst = int(v.shape[0]), int(nsrc), int(ndst)
+    if nsrc < 0 or ndst < 0 or int(v.shape[1]) != nsrc:
+        raise ValueError(f"v must be (nrec, {nsrc}), got {tuple(v.shape)}")
+    if nsrc >= 2 ** 31:
+        raise ValueError("the source plane must hold fewer than 2^31 cells")
+    try:
+        slice_ptr, length, col, S = plan_tensors
+    except (TypeError, ValueError):
+        raise ValueError("plan_tensors must be (slice_ptr, len, col, S)") from None
+    for name, t, dt in (("slice_ptr", slice_ptr, torch.int64), ("len", length, torch.int32),
+                        ("col", col, torch.int32), ("S", S, torch.float64)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.dim() == 1 and t.is_contiguous()
+                and t.device == v.device):
+            raise ValueError(f"{name} must be a contiguous 1-D {dt} tensor on {v.device}")
+    nslices = -(-ndst // regrid_slice())
+    if slice_ptr.shape[0] != nslices + 1 or length.shape[0] != ndst or col.shape[0] != S.shape[0]:
+        raise ValueError(f"the table of {ndst} destinations needs slice_ptr ({nslices + 1},), len "
+                         f"({ndst},) and col and S of one length")
+    min_frac = float(min_frac)
+    if not 0.0 <= min_frac <= 1.0:  # (a NaN compares false)
+        raise ValueError(f"min_frac must lie in [0, 1], got {min_frac}")
+    out_dtype = v.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"out_dtype must be float32 or float64, got {out_dtype}")
+    out = torch.empty((nrec, ndst), dtype=out_dtype, device=v.device)
+    if nrec == 0 or ndst == 0:
+        return out
+    flags = (_lib.REGRID_PROPAGATE if propagate else 0) | (0 if renorm else _lib.REGRID_NO_RENORM)
+    _call(lib, "mlx_regrid_apply", v.device, _ptr(v), vdt, _ptr(slice_ptr), _ptr(length), _ptr(col),
+          _ptr(S), int(S.shape[0]), min_frac, flags, nrec, nsrc, ndst, _ptr(out),
+          DTYPE_F64 if out_dtype == torch.float64 else DTYPE_F32)
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # order statistics (include/momlevel_quantile.h; csrc/momlevel_quantile.hip).  EXTENSION.
 # ---------------------------------------------------------------------------------------
 def quantile_block_cells(dtype=torch.float64):

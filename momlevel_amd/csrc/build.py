@@ -39,6 +39,7 @@ FEATURES = {
     "eof": ["eos_device.hpp", "mlx_internal.hpp", "mlx_pack.hpp", "mlx_record.hpp",
             "include/momlevel_eof.h"],
     "smooth": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_smooth.h"],
+    "regrid": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_regrid.h"],
 }
 
 
@@ -166,6 +167,11 @@ def eof_source_sha():
 def smooth_source_sha():
     """the horizontal-filter kernels' own guard: csrc/momlevel_smooth.hip (+ what it includes, + flags)"""
     return feature_source_sha("smooth")
+
+
+def regrid_source_sha():
+    """the remap kernel's own guard: csrc/momlevel_regrid.hip (+ what it includes, + flags)"""
+    return feature_source_sha("regrid")
 
 
 def hipcc():
