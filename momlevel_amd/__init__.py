@@ -9,7 +9,7 @@ C ABI (include/momlevel_hip.h, include/momlevel_trend.h, include/momlevel_clim.h
 include/momlevel_gauge.h, include/momlevel_spice.h, include/momlevel_vort.h,
 include/momlevel_area.h, include/momlevel_layer.h, include/momlevel_filter.h,
 include/momlevel_quantile.h, include/momlevel_column.h, include/momlevel_eof.h,
-include/momlevel_smooth.h, include/momlevel_regrid.h).
+include/momlevel_smooth.h, include/momlevel_regrid.h, include/momlevel_census.h).
 
 ``tidegauge.extract_tidegauge`` takes a ``(..., yh, xh)`` record to its tide gauges: the nearest
 wet grid point of every gauge by great-circle distance (a brute-force search on the GPU, ties to
@@ -73,6 +73,13 @@ lat/lon grids), ``nearest_weights`` or any ESMF-style table through ``from_tripl
 generated, the tripolar fold is not part of the coarsening's periodic option and a table is not
 spread over ranks (include/momlevel_regrid.h).
 
+``census`` (an EXTENSION too) is the scatter: ``histogram`` counts, or sums a weight or a weighted
+value over, the cells of every class of one or two fields per record -- ``ts_census`` is the
+volumetric theta-S census, ``histogram(calc_pdens, calc_spice, weights=volcello)`` the sigma-pi one
+-- in a fixed order of summation without atomics; tables larger than one launch go in bin groups;
+more than two binning fields, a fused density and multi-rank tables are not built
+(include/momlevel_census.h).
+
 Everything else in momlevel (plots, the xgcm grid object itself, ...) is out of scope -- use momlevel.
 
 There is no CPU fallback: without libmomlevel_hip.so and a HIP device the compute
@@ -81,6 +88,7 @@ entry points raise ``MomlevelHipError``.
 
 __version__ = "0.1.0"
 
+from . import census
 from . import derived
 from . import dynamic
 from . import eof
@@ -114,6 +122,7 @@ __all__ = [
     "DataArray",
     "Dataset",
     "MomlevelHipError",
+    "census",
     "derived",
     "dynamic",
     "inverse_barometer",

@@ -62,6 +62,8 @@ GRAM_MAX_SPLIT = 32
 SMOOTH_FILL, SMOOTH_RESIDUAL = 1, 2
 # ---- constants mirrored from include/momlevel_regrid.h -----------------------------
 REGRID_PROPAGATE, REGRID_NO_RENORM = 1, 2
+# ---- constants mirrored from include/momlevel_census.h -----------------------------
+CENSUS_CLOSED_0, CENSUS_CLOSED_1 = 1, 2  # bits of mlx_census_histogram's `closed`
 # ---- constants mirrored from include/momlevel_path.h -------------------------------
 PATH_GENERIC, PATH_FAST, PATH_FAST_P3D = 0, 1, 2
 PATH_ALIGNED_T, PATH_ALIGNED_S, PATH_ALIGNED_OUT, PATH_ALIGNED_P = 1, 2, 4, 8
@@ -290,6 +292,19 @@ REGRID_PROTOTYPES = {
 }
 
 
+# The census (include/momlevel_census.h): bound by load_census() on first use, for the same reason.
+# (Named as EOF_PROTOTYPES is, for the same count.)
+CENSUS_PROTOTYPES = {
+    "mlx_census_tile": (_i64, []),
+    "mlx_census_blocks": (_i64, [_i64]),
+    "mlx_census_max_bins": (_i64, [_int, _int, _int]),
+    "mlx_census_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int]),
+    "mlx_census_histogram": (_int, [_vp, _int, _vp, _int, _int, _vp, _i64, _vp, _i64, _int, _vp,
+                                    _int, _int, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _sz,
+                                    _vp]),
+}
+
+
 # The path queries of the pointwise EOS entry points (include/momlevel_path.h): bound by
 # load_path() on first use, for the same reason.  (They live in csrc/momlevel_hip.hip and
 # csrc/momlevel_promote.hip, beside the launchers that go by them.)
@@ -371,13 +386,14 @@ _GROUPS = {
     "eof": (EOF_PROTOTYPES, "the Gram kernels"),
     "smooth": (SMOOTH_PROTOTYPES, "the horizontal-filter kernels"),
     "regrid": (REGRID_PROTOTYPES, "the remap kernel"),
+    "census": (CENSUS_PROTOTYPES, "the census kernels"),
 }
 
 
 # what is bound: one module flag per group (the host tests reset them by name)
 _trend_bound = _clim_bound = _gauge_bound = _spice_bound = _vort_bound = _area_bound = False
 _layer_bound = _filter_bound = _path_bound = _quantile_bound = _column_bound = _eof_bound = False
-_smooth_bound = _regrid_bound = False
+_smooth_bound = _regrid_bound = _census_bound = False
 
 
 def _load_group(group):
@@ -445,6 +461,10 @@ def load_smooth():
 
 def load_regrid():
     return _load_group("regrid")
+
+
+def load_census():
+    return _load_group("census")
 
 
 def last_error():

@@ -1961,6 +1961,106 @@ def regrid_apply(v, plan_tensors, nsrc, ndst, min_frac=0.0, propagate=False, ren
 
 
 # ---------------------------------------------------------------------------------------
+# the census (include/momlevel_census.h; csrc/momlevel_census.hip).  EXTENSION.
+# ---------------------------------------------------------------------------------------
+def census_tile():
+    """Cells of one tile of the census (mlx_census_tile): a thread owns four consecutive cells."""
+    return int(_lib.load_census().mlx_census_tile())
+
+
+def census_blocks(ncells):
+    """Blocks that share one record of ``ncells`` cells (mlx_census_blocks): a pure function of
+    ``ncells``, and with it the order of summation."""
+    return int(_lib.load_census().mlx_census_blocks(int(ncells)))
+
+
+def census_max_bins(nfields=1, has_weights=False, has_values=False):
+    """The most bins of one launch (mlx_census_max_bins): larger tables go in bin groups."""
+    return int(_lib.load_census().mlx_census_max_bins(int(nfields), int(bool(has_weights)),
+                                                      int(bool(has_values))))
+
+
+def census_workspace_bytes(nrec, ncells, nbins, has_weights=False, has_values=False):
+    """Bytes of partials one launch needs (mlx_census_workspace_bytes)."""
+    return int(_lib.load_census().mlx_census_workspace_bytes(
+        int(nrec), int(ncells), int(nbins), int(bool(has_weights)), int(bool(has_values))))
+
+
+def census(fields, edges, weights=None, values=None, closed=3):
+    """One launch of the census (mlx_census_histogram; include/momlevel_census.h states the
+    contract, tests/census_numpy.py restates it): ``fields`` one or two (nrec, ncells) contiguous
+    float32 / float64 device tensors, ``edges`` one contiguous 1-D float64 device tensor of
+    ``n_d + 1`` edges per field (their values are the caller's: whatever they hold, the kernel
+    writes nothing outside its tables), ``weights`` None, (ncells,) or (nrec, ncells), ``values``
+    None or (nrec, ncells) and only with weights.  ``closed``: bit d set when a value on the last
+    edge of field d belongs to its last bin (3 for a whole table; a bin group clears the bit of a
+    field whose last edge is not the table's).  Returns ``(count, wsum, vsum)``: (nrec, nbins) int64
+    and float64 tensors, nbins = n_0 (* n_1), ``wsum`` / ``vsum`` None without weights / values.
+    More bins than ``census_max_bins`` are a ``ValueError``: launch in groups
+    (momlevel_amd/census.py).  It takes no result buffer, as ``regrid_apply``; the results are new
+    tensors, checked against the operands like every other result."""
+    require_device()
+    lib = _lib.load_census()
+    fields, edges = tuple(fields), tuple(edges)
+    D = len(fields)
+    if D not in (1, 2) or len(edges) != D:
+        raise ValueError("the census bins by one or two fields, with one edge array each")
+    codes = [_float_code(f, f"fields[{d}]", 2) for d, f in enumerate(fields)]
+    dev = fields[0].device
+    nrec, ncells = (int(n) for n in fields[0].shape)
+    if D == 2 and (tuple(fields[1].shape) != (nrec, ncells) or fields[1].device != dev):
+        raise ValueError(f"fields[1] must be ({nrec}, {ncells}) on {dev}")
+    for d, e in enumerate(edges):
+        if not (isinstance(e, torch.Tensor) and e.dtype == torch.float64 and e.dim() == 1
+                and e.is_contiguous() and e.device == dev and e.numel() >= 2):
+            raise ValueError(f"edges[{d}] must be a contiguous 1-D float64 tensor of at least two "
+                             f"edges on {dev}")
+    n = [int(e.numel()) - 1 for e in edges] + [1] * (2 - D)
+    nbins = n[0] * n[1]
+    if values is not None and weights is None:
+        raise ValueError("values need weights: the sum is of weights * values")
+    cap = census_max_bins(D, weights is not None, values is not None)
+    if nbins > cap:
+        raise ValueError(f"{nbins} bins are more than the {cap} of one launch: launch in bin groups")
+    wdt = vdt = DTYPE_F64
+    per_record = 0
+    if weights is not None:
+        wdt = _float_code(weights, "weights")
+        per_record = int(weights.dim() == 2)
+        if tuple(weights.shape) not in ((ncells,), (nrec, ncells)) or weights.device != dev:
+            raise ValueError(f"weights must be ({ncells},) or ({nrec}, {ncells}) on {dev}")
+    if values is not None:
+        vdt = _float_code(values, "values", 2)
+        if tuple(values.shape) != (nrec, ncells) or values.device != dev:
+            raise ValueError(f"values must be ({nrec}, {ncells}) on {dev}")
+    if int(closed) not in (0, 1, 2, 3):
+        raise ValueError(f"closed must be 0 .. 3, got {closed}")
+    count = _out_like(None, (nrec, nbins), torch.int64, dev)
+    wsum = None if weights is None else _out_like(None, (nrec, nbins), torch.float64, dev)
+    vsum = None if values is None else _out_like(None, (nrec, nbins), torch.float64, dev)
+    if nrec == 0:
+        return count, wsum, vsum
+    if ncells == 0:  # numpy: the sum of nothing is 0
+        return count.zero_(), None if wsum is None else wsum.zero_(), \
+            None if vsum is None else vsum.zero_()
+    nbytes = census_workspace_bytes(nrec, ncells, nbins, weights is not None, values is not None)
+    if nbytes == 0:
+        raise ValueError(f"a census of {nrec} records of {ncells} cells is more than one launch "
+                         "takes: window the records")
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    _no_overlap([("count", count), ("wsum", wsum), ("vsum", vsum), ("workspace", ws)],
+                [(f"fields[{d}]", f) for d, f in enumerate(fields)]
+                + [(f"edges[{d}]", e) for d, e in enumerate(edges)]
+                + [("weights", weights), ("values", values)])
+    _call(lib, "mlx_census_histogram", dev, _ptr(fields[0]), codes[0],
+          _ptr(fields[1]) if D == 2 else None, codes[1] if D == 2 else DTYPE_F64, D,
+          _ptr(edges[0]), n[0], _ptr(edges[1]) if D == 2 else None, n[1], int(closed),
+          _ptr(weights), wdt, per_record, _ptr(values), vdt, nrec, ncells, _ptr(count),
+          _ptr(wsum), _ptr(vsum), _ptr(ws), nbytes)
+    return count, wsum, vsum
+
+
+# ---------------------------------------------------------------------------------------
 # order statistics (include/momlevel_quantile.h; csrc/momlevel_quantile.hip).  EXTENSION.
 # ---------------------------------------------------------------------------------------
 def quantile_block_cells(dtype=torch.float64):

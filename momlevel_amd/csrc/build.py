@@ -40,6 +40,7 @@ FEATURES = {
             "include/momlevel_eof.h"],
     "smooth": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_smooth.h"],
     "regrid": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_regrid.h"],
+    "census": ["mlx_internal.hpp", "mlx_pack.hpp", "include/momlevel_census.h"],
 }
 
 
@@ -172,6 +173,11 @@ def smooth_source_sha():
 def regrid_source_sha():
     """the remap kernel's own guard: csrc/momlevel_regrid.hip (+ what it includes, + flags)"""
     return feature_source_sha("regrid")
+
+
+def census_source_sha():
+    """the census kernels' own guard: csrc/momlevel_census.hip (+ what it includes, + flags)"""
+    return feature_source_sha("census")
 
 
 def hipcc():
