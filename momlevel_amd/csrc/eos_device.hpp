@@ -112,9 +112,13 @@ struct Lanes<f2> {
 // and the sequence is the seven instructions of rcp_scale_free() below -- bit-identical to the
 // IEEE expansion for 2^-1000 < |den| < 2^1000 and trivially equivalent (NaN) for a NaN den, i.e.
 // on land.  scripts/check_div.hip measured where it is NOT (profiles/r03_check_div.log): denormal
-// den (v_rcp_f64 of a denormal differs from the scaled sequence), |den| within a few binades of
-// 2^-1024 and of 2^1022 -- so a class test of the seed alone (is it 0, inf, denormal?) is not
-// enough, the guard has to be a two-sided window with a margin.  Two forms:
+// den (v_rcp_f64 of a denormal differs from the scaled sequence) and |den| within a few binades of
+// 2^-1024 -- so a class test of the seed alone (is it 0, inf, denormal?) is not enough, the guard
+// has to be a window with a margin on the LOW side.  On the HIGH side the margin is symmetry, not
+// need, on gfx950: v_rcp_f64 returns a denormal seed unflushed and every later step is one
+// correctly rounded fma, so den in the binades 1022 / 1023 came out with the IEEE bits on every
+// operand tried (the planted cells of tests/eos_extremes.py and the random-mantissa sweep DESIGN.md
+// reports); the bound stays at 2^1000 because nothing is gained by moving it.  Two forms:
 //   * window on den, two ordered compares (a NaN den passes both): any float64 operands;
 //   * ONE v_cmp_class on the seed (0 / inf / denormal?) where the window's margins hold by
 //     construction: numpy's float32 polynomial.  There al0, p0, lam are float32 VALUES, so a
@@ -131,9 +135,14 @@ constexpr int kClassNotNanNorNormal = 0x004 | 0x010 | 0x020 | 0x040 | 0x080 | 0x
 // no VALU work beyond the compares themselves.  Written as the instructions they are: through
 // __builtin_amdgcn_ballot_w64(...) this compiler (ROCm 7.2 clang) round-trips every lane mask
 // through a v_cndmask / v_cmp_ne pair.
+// The seed comes straight out of v_rcp_f64, a transcendental-unit instruction: on gfx940 / gfx950 a
+// non-transcendental VALU instruction that reads such a result needs one wait state after it.  The
+// compiler pads its own instructions, but it does not look into inline assembly and may put the
+// compare directly behind the v_rcp_f64, where it would read the register's OLD contents.  Hence the
+// s_nop: the wait state, whatever the schedule ("The guard inside the kernels").
 __device__ __forceinline__ lanemask_t lanes_not_nan_nor_normal(double y) {
   lanemask_t m;
-  asm("v_cmp_class_f64 %0, %1, %2" : "=s"(m) : "v"(y), "s"(kClassNotNanNorNormal));
+  asm("s_nop 0\n\tv_cmp_class_f64 %0, %1, %2" : "=s"(m) : "v"(y), "s"(kClassNotNanNorNormal));
   return m;
 }
 // lanes whose |x| is outside (2^-1000, 2^1000); NaN is inside (ordered compares are false on NaN)
@@ -234,9 +243,16 @@ struct FusedOps {
     return __builtin_fma(a, b, c);
   }
   // Unguarded: nothing here has to match numpy's bits, and the Wright denominator of any ocean
-  // state lives near 2^19.  A denominator of exactly 0, inf or a denormal (temperatures and
-  // salinities hundreds of units outside the fit's range) yields NaN -- skipped by the sums -- where
-  // numpy yields inf / 0.  (Round 3 measured the class guard of ExactFastF32Ops on this policy too:
+  // state lives near 2^19.  Measured on the operands of tests/eos_extremes.py
+  // (tests/test_gpu_eos_extremes.py::test_fused_policy_per_class_of_den): a den of +-inf (an
+  // overflow of al0 * num from finite operands included) yields NaN -- skipped by the sums -- where
+  // numpy yields 0; every FINITE |den| up to the largest double, the top binades included, stays
+  // within 1.5e-14 of numpy (v_rcp_f64 returns a denormal seed unflushed and the correction works
+  // on it).  NOT measured, derived: where v_rcp_f64 returns inf (den == 0, or a denormal small
+  // enough) e is NaN or -+inf and the result NaN, where numpy yields inf; no operand of that record
+  // reaches such a den HERE, because this policy rounds its OWN den (pressure folded into B0, one
+  // fma): where numpy's den vanishes by cancellation this one does not, and the result is a finite
+  // number of no meaning.  (Round 3 measured the class guard of ExactFastF32Ops on this policy too:
   // +2 instructions per cell and -4.5 % on the thermosteric sums, profiles/r03_variants_summary.json
   // -- not worth it for inputs that are not sea water.)
   static __device__ __forceinline__ double quotient(double num, double den, lanemask_t&) {

@@ -7,7 +7,7 @@ Run ONCE in the build container, where /root/reference exists:
 (-B: the process is root, a plain import would drop __pycache__ into the
 read-only reference tree.)
 
-Three files are written:
+Four files are written:
 
 * ``wright_vectors.npz`` and ``wright_vectors_mixed.npz`` (section (8)) --
   inputs and the outputs of the REFERENCE'S OWN ``src/momlevel/eos/wright.py`` (loaded standalone with importlib: the module
@@ -18,6 +18,9 @@ Three files are written:
   reference's ``generate_test_data()`` datasets, for the quantities the
   reference's own tests do not pin tightly (the ``domain="global"`` variants:
   tests/test_steric.py:80-125 are atol-dominated).  Labelled "oracle-pinned".
+
+* ``wright_extremes.npz`` (section (11); ``make_golden.py extremes`` writes it alone) -- the
+  operands of tests/eos_extremes.py and the reference's density on them.
 
 The text of no reference source file is stored: only numbers.
 """
@@ -48,6 +51,48 @@ def load_reference_linear():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def write_extremes(ref):
+    # (11) operands at which the guard of the kernels' reciprocal must object (tests/eos_extremes.py:
+    # denominators in chosen binades either side of 2^1000, exact zeros, overflows, pressures either
+    # side of 2^-200 and 2^800, each alone in its wave), float64 and float32, under the pressure
+    # profile and under the (z,y,x) and (t,z,y,x) pressure fields that carry the level's pressure in
+    # one lane of a wave: what the REFERENCE's density returns there.  A file of its own.
+    sys.path.insert(0, os.path.dirname(HERE))
+    import eos_extremes
+    from oracle import momlevel_numpy as o
+
+    ext = {}
+    for prec in ("f64", "f32"):
+        case = eos_extremes.build_case(prec)
+        T, S = case["T"], case["S"]
+        for k in ("T", "S", "pz", "p3d", "p4d", "c0", "c1", "planted"):
+            ext[f"{prec}_{k}"] = case[k]
+        ext[f"{prec}_plant_kinds"] = np.array([k for k, _, _, _ in case["plants"]])
+        ext[f"{prec}_plant_cells"] = np.array([[t, z, c] for _, t, z, c in case["plants"]])
+        with np.errstate(all="ignore"):
+            for form, p in (("prof", case["pz"][:, None, None]), ("p3d", case["p3d"]), ("p4d", case["p4d"])):
+                ext[f"{prec}_rho_{form}"] = ref.density(T, S, p)
+                assert ext[f"{prec}_rho_{form}"].dtype == np.float64
+            # the float32 record upcast ("upcast") and with ONE field upcast (theta / S of different
+            # dtypes: "mixT32" theta float32, "mixS32" S float32): the density is stored; the
+            # derivatives are not (the file would outgrow wright_vectors.npz) -- the reference agrees
+            # with the oracle on them bit for bit, HERE, and the tests take the oracle
+            mixes = {"": (T, S)}
+            if prec == "f32":
+                mixes.update(upcast=(T.astype(np.float64), S.astype(np.float64)),
+                             mixT32=(T, S.astype(np.float64)), mixS32=(T.astype(np.float64), S))
+            for tag, (a, b) in mixes.items():
+                for form, p in (("prof", case["pz"][:, None, None]), ("p3d", case["p3d"]), ("p4d", case["p4d"])):
+                    if tag:
+                        ext[f"{prec}_rho_{form}_{tag}"] = ref.density(a, b, p)
+                    for fn in ("density", "drho_dtemp", "drho_dsal", "alpha", "beta"):
+                        assert eos_extremes.same_bits(getattr(ref, fn)(a, b, p),
+                                                      o.eos_func_from_str("wright", fn)(a, b, p)) == 0
+    np.savez_compressed(os.path.join(HERE, "wright_extremes.npz"), **ext)
+    assert (os.path.getsize(os.path.join(HERE, "wright_extremes.npz"))
+            <= os.path.getsize(os.path.join(HERE, "wright_vectors.npz")))
 
 
 def main():
@@ -207,6 +252,8 @@ def main():
     np.savez_compressed(os.path.join(HERE, "wright_vectors_mixed.npz"),
                         **{k: v for k, v in out.items() if k.startswith("mix_")})
 
+    write_extremes(ref)
+
     # ---- oracle-pinned steric cases on the reference's test dataset ----------
     from oracle import momlevel_numpy as o
 
@@ -235,4 +282,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["extremes"]:  # section (11) alone: the other files stay as they are
+        write_extremes(load_reference_wright())
+    else:
+        main()
