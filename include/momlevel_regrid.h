@@ -77,6 +77,13 @@ extern "C" {
 int64_t mlx_regrid_slice(void);
 int64_t mlx_regrid_record_window(void);
 
+/* Block rows along the records (gridDim.y) of a call over nrec records:
+ * min(ceil(nrec / mlx_regrid_record_window()), cap).  Up to the cap a block row carries one window
+ * of records; past it a row goes on to the window cap rows further, and so on.  Host arithmetic
+ * only, the rule the launch itself goes by; a record's bits do not depend on it.  0 for nrec <= 0
+ * or nrec > 2^38. */
+int mlx_regrid_window_rows(int64_t nrec);
+
 /* v: (nrec, nsrc) C-contiguous, MLX_DTYPE_F64 or MLX_DTYPE_F32 (dtype); slice_ptr:
  * (ceil(ndst / mlx_regrid_slice()) + 1) int64; len: (ndst) int32; col: (nentries) int32; S:
  * (nentries) float64; out: (nrec, ndst), MLX_DTYPE_F64 or MLX_DTYPE_F32 (out_dtype).  All on the

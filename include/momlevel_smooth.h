@@ -74,6 +74,19 @@ int64_t mlx_smooth_tile_w(int dtype);
 int64_t mlx_smooth_max_window(void);
 int64_t mlx_smooth_record_window(void);
 
+/* Block rows along the records (gridDim.y) of a call that goes cell by cell over nrec records:
+ * min(nrec, cap).  Up to the cap a block row carries one record; past it a row goes on to the
+ * record cap rows further, and so on.  Host arithmetic only, the rule the launch itself goes by; a
+ * record's bits do not depend on it.  0 for nrec <= 0 or nrec > 2^38. */
+int mlx_smooth_record_rows(int64_t nrec);
+
+/* 1 when a call of these extents takes the tiled path, given v and out on 16-byte boundaries:
+ * Wx, Wy <= mlx_smooth_max_window(), nx a multiple of 4, ny >= mlx_smooth_tile_h() and nx >= the
+ * tile's width.  0 otherwise, and for extents that mlx_smooth_apply refuses (ny or nx < 1,
+ * ny * nx > 2^38, Wx outside [1, nx], Wy outside [1, ny]).  Host arithmetic only, the rule
+ * mlx_smooth_apply itself goes by. */
+int mlx_smooth_tiled(int64_t Wx, int64_t Wy, int64_t ny, int64_t nx);
+
 /* v: (nrec, ny, nx) C-contiguous, MLX_DTYPE_F64 or MLX_DTYPE_F32 (dtype); area: (ny, nx),
  * MLX_DTYPE_F64 or MLX_DTYPE_F32 (area_dtype); wx: float64, wx_stride == 0: Wx weights for every
  * source row, wx_stride == Wx: a table (ny, Wx), row r for source row r; wy: Wy float64 weights;

@@ -277,6 +277,8 @@ SMOOTH_PROTOTYPES = {
     "mlx_smooth_tile_w": (_i64, [_int]),
     "mlx_smooth_max_window": (_i64, []),
     "mlx_smooth_record_window": (_i64, []),
+    "mlx_smooth_record_rows": (_int, [_i64]),
+    "mlx_smooth_tiled": (_int, [_i64, _i64, _i64, _i64]),
     "mlx_smooth_apply": (_int, [_vp, _int, _vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _int,
                                _i64, _int, _i64, _i64, _i64, _vp, _int, _vp]),
 }
@@ -287,6 +289,7 @@ SMOOTH_PROTOTYPES = {
 REGRID_PROTOTYPES = {
     "mlx_regrid_slice": (_i64, []),
     "mlx_regrid_record_window": (_i64, []),
+    "mlx_regrid_window_rows": (_int, [_i64]),
     "mlx_regrid_apply": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _dbl, _int, _i64, _i64, _i64,
                                _vp, _int, _vp]),
 }

@@ -1812,6 +1812,20 @@ def smooth_record_window():
     return int(_lib.load_smooth().mlx_smooth_record_window())
 
 
+def smooth_record_rows(nrec):
+    """Block rows along the records of a call of ``nrec`` records that goes cell by cell
+    (mlx_smooth_record_rows): ``min(nrec, cap)``; past the cap a row goes on to further records.
+    The results do not depend on it."""
+    return int(_lib.load_smooth().mlx_smooth_record_rows(int(nrec)))
+
+
+def smooth_tiled(Wx, Wy, ny, nx):
+    """1 when a call of a ``Wy`` x ``Wx`` window on a ``(ny, nx)`` plane takes the tiled path, given
+    ``v`` and ``out`` on 16-byte boundaries (mlx_smooth_tiled); 0 when it goes cell by cell, and
+    for extents that mlx_smooth_apply refuses.  The results do not depend on it."""
+    return int(_lib.load_smooth().mlx_smooth_tiled(int(Wx), int(Wy), int(ny), int(nx)))
+
+
 def smooth_weights(wx, wy, ny, nx):
     """The host-side mirror of the weights as the kernel reads them: float64, ``wx`` ``(Wx,)`` (one
     row for every source row) or ``(ny, Wx)`` (row r for source row r), ``wy`` ``(Wy,)``,
@@ -1906,6 +1920,13 @@ def regrid_slice():
 def regrid_record_window():
     """Records a block walks on one read of its table entries (mlx_regrid_record_window)."""
     return int(_lib.load_regrid().mlx_regrid_record_window())
+
+
+def regrid_window_rows(nrec):
+    """Block rows along the records of a call of ``nrec`` records (mlx_regrid_window_rows):
+    ``min(ceil(nrec / regrid_record_window()), cap)``; past the cap a row goes on to further
+    windows of records.  The results do not depend on it."""
+    return int(_lib.load_regrid().mlx_regrid_window_rows(int(nrec)))
 
 
 def regrid_apply(v, plan_tensors, nsrc, ndst, min_frac=0.0, propagate=False, renorm=True,

@@ -160,10 +160,18 @@ __global__ __launch_bounds__(kRgBlock) void k_regrid(const RegridArgs g) {
   }
 }
 
+// gridDim.y of a call over nrec > 0 records: one block row per window of kRgRecWin records up to the
+// cap, past which the rows stride.  The one rule: mlx_regrid_window_rows reports it, the launch
+// uses it.
+inline int64_t regrid_window_rows(int64_t nrec) {
+  const int64_t nwin = ceil_div(nrec, kRgRecWin);
+  return nwin < (int64_t)kRgMaxGridY ? nwin : (int64_t)kRgMaxGridY;
+}
+
 template <typename TV, typename TO>
 void regrid_launch(const RegridArgs& g, int mode, hipStream_t st) {
-  const int64_t ny = g.nwin < kRgMaxGridY ? g.nwin : kRgMaxGridY;
-  const dim3 grid((unsigned)ceil_div(g.nslices, kRgWaves), (unsigned)ny), block(kRgBlock);
+  const dim3 grid((unsigned)ceil_div(g.nslices, kRgWaves), (unsigned)regrid_window_rows(g.nrec)),
+      block(kRgBlock);
   if (mode == kRgPropagate)
     hipLaunchKernelGGL((k_regrid<TV, TO, kRgPropagate>), grid, block, 0, st, g);
   else if (mode == kRgNoRenorm)
@@ -183,6 +191,11 @@ inline bool rg_overlap(const void* a, size_t na, const void* b, size_t nb) {
 extern "C" int64_t mlx_regrid_slice(void) { return mlx::kRgSlice; }
 
 extern "C" int64_t mlx_regrid_record_window(void) { return mlx::kRgRecWin; }
+
+extern "C" int mlx_regrid_window_rows(int64_t nrec) {
+  if (nrec <= 0 || nrec > mlx::kRgMaxCells) return 0;
+  return (int)mlx::regrid_window_rows(nrec);
+}
 
 extern "C" int mlx_regrid_apply(const void* v, int dtype, const int64_t* slice_ptr,
                                 const int32_t* len, const int32_t* col, const double* S,

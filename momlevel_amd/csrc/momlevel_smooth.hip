@@ -49,6 +49,7 @@ constexpr int kSmTW = 64;      // output columns of a tile: one per lane of the 
 constexpr int kSmAlign = 4;    // cells the staged columns start on a multiple of (16 bytes of float32)
 constexpr int kSmMaxWindow = 33;
 constexpr int kSmRecWin = 8;
+constexpr int kSmMaxGridY = 65535;
 constexpr int64_t kSmMaxCells = (int64_t)1 << 38;
 // the window classes of the tiled kernel: static LDS of 49.6, 58.8 and 124.4 KiB -- 3, 2 and 1 blocks per CU
 constexpr int kSmClassS = 5, kSmClassM = 9, kSmClassL = kSmMaxWindow;
@@ -325,6 +326,19 @@ __global__ __launch_bounds__(kSmBlock) void k_smooth_cells(const SmoothArgs g) {
   }
 }
 
+// gridDim.y of k_smooth_cells over nrec > 0 records: one block row per record up to the cap, past
+// which the rows stride.  The one rule: mlx_smooth_record_rows reports it, the launch uses it.
+inline int64_t smooth_record_rows(int64_t nrec) {
+  return nrec < (int64_t)kSmMaxGridY ? nrec : (int64_t)kSmMaxGridY;
+}
+
+// the shape part of the choice of path, for extents mlx_smooth_apply accepts: windows the LDS of a
+// class holds, rows of whole packs, a plane of at least one tile each way.  The one rule:
+// mlx_smooth_tiled reports it, mlx_smooth_apply goes by it (and by the alignment of v and out).
+inline bool smooth_tiled_shape(int64_t Wx, int64_t Wy, int64_t ny, int64_t nx) {
+  return Wx <= kSmMaxWindow && Wy <= kSmMaxWindow && nx % kSmAlign == 0 && ny >= kSmTH && nx >= kSmTW;
+}
+
 template <typename TV, typename TA, typename TO>
 void smooth_launch(const SmoothArgs& g, bool tiled, hipStream_t st) {
   if (tiled) {
@@ -338,8 +352,8 @@ void smooth_launch(const SmoothArgs& g, bool tiled, hipStream_t st) {
     else
       hipLaunchKernelGGL((k_smooth_tiled<TV, TA, TO, kSmClassL>), grid, block, 0, st, g);
   } else {
-    const int64_t recs = g.nrec < 65535 ? g.nrec : 65535;
-    const dim3 grid((unsigned)ceil_div(g.ny * g.nx, kSmBlock), (unsigned)recs), block(kSmBlock);
+    const dim3 grid((unsigned)ceil_div(g.ny * g.nx, kSmBlock), (unsigned)smooth_record_rows(g.nrec)),
+        block(kSmBlock);
     hipLaunchKernelGGL((k_smooth_cells<TV, TA, TO>), grid, block, 0, st, g);
   }
 }
@@ -365,6 +379,17 @@ extern "C" int64_t mlx_smooth_tile_w(int dtype) { return mlx::is_float_dtype(dty
 extern "C" int64_t mlx_smooth_max_window(void) { return mlx::kSmMaxWindow; }
 
 extern "C" int64_t mlx_smooth_record_window(void) { return mlx::kSmRecWin; }
+
+extern "C" int mlx_smooth_record_rows(int64_t nrec) {
+  if (nrec <= 0 || nrec > mlx::kSmMaxCells) return 0;
+  return (int)mlx::smooth_record_rows(nrec);
+}
+
+extern "C" int mlx_smooth_tiled(int64_t Wx, int64_t Wy, int64_t ny, int64_t nx) {
+  using namespace mlx;
+  if (ny < 1 || nx < 1 || ny > kSmMaxCells / nx || Wx < 1 || Wx > nx || Wy < 1 || Wy > ny) return 0;
+  return smooth_tiled_shape(Wx, Wy, ny, nx) ? 1 : 0;
+}
 
 extern "C" int mlx_smooth_apply(const void* v, int dtype, const void* area, int area_dtype,
                                 const double* wx, int64_t Wx, int64_t wx_stride, int64_t lead_x,
@@ -413,8 +438,7 @@ extern "C" int mlx_smooth_apply(const void* v, int dtype, const void* area, int 
   // (Wx, Wy beyond int only reach the generic kernel through nx, ny > 2^31: refuse the cast)
   if (Wx > (int64_t)1 << 30 || Wy > (int64_t)1 << 30)
     return fail(MLX_E_SHAPE, "need Wx and Wy <= 2^30");
-  const bool tiled = Wx <= kSmMaxWindow && Wy <= kSmMaxWindow && nx % kSmAlign == 0 &&
-                     ny >= kSmTH && nx >= kSmTW && aligned(v, 16) && aligned(out, 16);
+  const bool tiled = smooth_tiled_shape(Wx, Wy, ny, nx) && aligned(v, 16) && aligned(out, 16);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool v64 = dtype == MLX_DTYPE_F64, a64 = area_dtype == MLX_DTYPE_F64;
   if (v64) {

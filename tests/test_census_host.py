@@ -64,7 +64,7 @@ def test_other_tables_and_the_abi_version_are_untouched():
     for name in _lib.CENSUS_PROTOTYPES:
         for table in others + [_lib.EOF_PROTOTYPES, _lib.SMOOTH_PROTOTYPES, _lib.REGRID_PROTOTYPES]:
             assert name not in table
-    assert len(_lib.SIGNATURES) == 28 and len(_lib.REGRID_PROTOTYPES) == 3
+    assert len(_lib.SIGNATURES) == 28 and len(_lib.REGRID_PROTOTYPES) == 4
     assert _lib.ABI_VERSION == 9 and _lib.load().mlx_version() == 9
     assert _lib._GROUPS["census"][0] is _lib.CENSUS_PROTOTYPES and _lib._census_bound in (True, False)
     assert "MLX_ABI_VERSION" not in open(HEADER).read().replace("do not move MLX_ABI_VERSION", "")

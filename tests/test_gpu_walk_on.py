@@ -20,6 +20,14 @@ records fit one tile a block and one launch a call.
     ``t = t_base + blockIdx.z`` in k_eos_map: a record of more steps than one launch of the pointwise
     EOS map takes (core.k0_path).  That walk-on is in test_gpu_eos_matrix.py
     (test_k0_past_one_launch), beside the rest of that entry point's dispatch.
+  * k_smooth_cells (csrc/momlevel_smooth.hip), ``for (rec = blockIdx.y; rec < nrec; rec += gridDim.y)``:
+    more records than block rows (core.smooth_record_rows at its cap) on the cell-by-cell path, a
+    plane of four cells.  Gates: smooth_numpy.plane_smooth, and the records around the stride as
+    calls of their own.
+  * k_regrid (csrc/momlevel_regrid.hip), ``for (win = blockIdx.y; win < nwin; win += gridDim.y)``:
+    more windows of records than block rows (core.regrid_window_rows at its cap), the last window
+    of one record.  Gates: regrid_numpy.apply_csr, and the records around the stride as calls of
+    their own.
 
 Every size comes from the library's queries at run time, every test asserts from the query that
 the path was taken and prints the geometry.  Each result is written into a buffer that was filled
@@ -34,6 +42,9 @@ OUT OF REACH, with the size at which each would first run; no test here gets the
   * the filter's cap of 65535 blocks along time: the target of 8192 blocks a launch never lets the
     time axis have that many;
   * k_gauge_nearest's ``part += gridDim.y``: mlx_gauge_nearest_split keeps the parts to one pass.
+The horizontal filter and the remap have no other such loop: k_smooth_tiled takes one block per
+(tile, record window) and k_regrid one per four slices along blockIdx.x, and the 2^38 cells a call
+may hold keep both below the 2^31 blocks of gridDim.x (2^30 at the most).
 """
 
 import numpy as np
@@ -42,11 +53,16 @@ import torch
 
 import filter_numpy as fn
 import layer_numpy as ln
+import regrid_numpy as rn
+import smooth_numpy as sn
 import vort_numpy as vn
 from conftest import assert_bit_equal
-from momlevel_amd import core
+from momlevel_amd import core, regrid
 from test_gpu_filter_edges import _modes
 from test_gpu_layer import _equals_restatement, _same_bits
+from test_gpu_regrid_edges import _abi as _regrid_abi
+from test_gpu_smooth import assert_same_bits
+from test_gpu_smooth_edges import _abi as _smooth_abi
 
 pytestmark = pytest.mark.gpu
 
@@ -312,4 +328,67 @@ def test_pv_second_launch_starts_whole_planes_in(interp, units):
     _check_both_sides(lambda z, n: core.potential_vorticity(z, f, n, **kw), whole, step, (zeta, n2),
                       f"pv interp={interp} {units}")
     del zeta, n2, out, whole
+    torch.cuda.empty_cache()
+
+
+# ---- the horizontal filter, cell by cell: more records than block rows --------------------------------
+@pytest.mark.parametrize("periodic", [True, False], ids=["periodic", "closed"])
+@pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
+def test_smooth_cells_record_rows_stride_past_the_cap(dtype, periodic):
+    cap = core.smooth_record_rows(1 << 30)
+    nrec = cap + 3  # the first three block rows take a second record
+    assert nrec <= 2 ** 17, nrec  # (65 538 today)
+    ny, nx, Wx, Wy = 1, 4, 3, 1
+    print(f"smooth {np.dtype(dtype).name} plane=({ny}, {nx}) window {Wy}x{Wx} periodic={periodic}: "
+          f"{nrec} records on {core.smooth_record_rows(nrec)} block rows (the cap: {cap})")
+    assert core.smooth_tiled(Wx, Wy, ny, nx) == 0  # cell by cell
+    assert core.smooth_record_rows(nrec) == cap == nrec - 3
+    rng = np.random.default_rng(nrec + int(periodic))
+    v = rng.normal(0.2, 1.0, (nrec, ny, nx))
+    v[rng.random(v.shape) < 0.1] = np.nan  # so that the records differ
+    v = v.astype(dtype)
+    area = np.array([[4.0e8, 9.0e8, 5.5e8, 7.0e8]])
+    wx, wy = np.array([0.25, 0.5, 0.3]), np.array([1.0])
+    want = sn.plane_smooth(v, area, wx, wy, 1, 0, periodic, 1, False, False, dtype)
+    assert np.isnan(want).any() and np.isfinite(want).mean() > 0.5
+    vd, ad, wxd, wyd = _dev(v), _dev(area), _dev(wx), _dev(wy)
+    out = torch.full((nrec, ny, nx), SENTINEL, dtype=_torch_dtype(dtype), device=DEV)
+    _smooth_abi(vd, ad, wxd, wyd, 1, 0, periodic, 1, 0, out)
+    what = f"smooth {np.dtype(dtype).name} periodic={periodic}"
+    assert_same_bits(out, want, what)
+    for rec in (cap - 1, cap, cap + 2):  # the last first record of a row, the first and last strided
+        one = torch.full((1, ny, nx), SENTINEL, dtype=_torch_dtype(dtype), device=DEV)
+        _smooth_abi(vd[rec:rec + 1], ad, wxd, wyd, 1, 0, periodic, 1, 0, one)
+        assert_same_bits(one, out[rec:rec + 1], f"{what}: record {rec} on its own")
+
+
+# ---- the remap: more windows of records than block rows -----------------------------------------------
+def test_regrid_window_rows_stride_past_the_cap():
+    R = core.regrid_record_window()
+    cap = core.regrid_window_rows(1 << 30)
+    nrec = R * cap + R + 1  # the first block row takes a second window, the second one of ONE record
+    assert nrec <= 2 ** 20, nrec  # (524 289 today: 21 MB in)
+    nwin = -(-nrec // R)
+    nsrc, ndst = 5, 3
+    print(f"regrid float64 nsrc={nsrc} ndst={ndst}: {nrec} records, {nwin} windows of {R} on "
+          f"{core.regrid_window_rows(nrec)} block rows (the cap: {cap})")
+    assert core.regrid_window_rows(nrec) == cap == nwin - 2
+    indptr = np.array([0, 2, 2, 5], dtype=np.int64)  # the second row is empty
+    col = np.array([0, 1, 2, 3, 4], dtype=np.int32)
+    S = np.array([1.25, 3.0, 2.5, 0.75, 4.0])
+    rng = np.random.default_rng(nrec)
+    v = rng.normal(0.2, 1.0, (nrec, nsrc))
+    v[rng.random(v.shape) < 0.1] = np.nan
+    want = rn.apply_csr(v, indptr, col, S, ndst)
+    assert np.isnan(want[:, 1]).all() and np.isnan(want[:, 0]).any() and np.isfinite(want).mean() > 0.5
+    vd = _dev(v)
+    packed = [_dev(a) for a in regrid.pack_rows(indptr, col, S, core.regrid_slice())]
+    out = torch.full((nrec, ndst), SENTINEL, dtype=torch.float64, device=DEV)
+    _regrid_abi(vd, packed, ndst, out)
+    assert_same_bits(out, want, "regrid float64")
+    for rec in (R * cap - 1, R * cap, nrec - 1):  # the last record before the stride, the first past
+        one = torch.full((1, ndst), SENTINEL, dtype=torch.float64, device=DEV)  # it, the last
+        _regrid_abi(vd[rec:rec + 1], packed, ndst, one)
+        assert_same_bits(one, out[rec:rec + 1], f"regrid: record {rec} on its own")
+    del vd, out
     torch.cuda.empty_cache()

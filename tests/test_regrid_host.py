@@ -19,7 +19,7 @@ from momlevel_amd.labeled import DataArray, Dataset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "momlevel_regrid.h")
-NAMES = ["mlx_regrid_apply", "mlx_regrid_record_window", "mlx_regrid_slice"]
+NAMES = ["mlx_regrid_apply", "mlx_regrid_record_window", "mlx_regrid_slice", "mlx_regrid_window_rows"]
 U = 2.0 ** -53
 
 
@@ -70,7 +70,7 @@ def test_other_tables_and_the_abi_version_are_untouched():
     for name in _lib.REGRID_PROTOTYPES:
         for table in others + [_lib.EOF_PROTOTYPES, _lib.SMOOTH_PROTOTYPES]:
             assert name not in table
-    assert len(_lib.SIGNATURES) == 28 and len(_lib.SMOOTH_PROTOTYPES) == 5
+    assert len(_lib.SIGNATURES) == 28 and len(_lib.SMOOTH_PROTOTYPES) == 7
     assert _lib.ABI_VERSION == 9 and _lib.load().mlx_version() == 9
     assert _lib._GROUPS["regrid"][0] is _lib.REGRID_PROTOTYPES
     assert "MLX_ABI_VERSION" not in open(HEADER).read().replace("does not move MLX_ABI_VERSION", "")
@@ -80,6 +80,19 @@ def test_geometry_queries():
     lib = _lib.load_regrid()
     assert core.regrid_slice() == lib.mlx_regrid_slice() == 64  # one lane per destination of a wave
     assert core.regrid_record_window() == lib.mlx_regrid_record_window() >= 1
+
+
+def test_launch_queries_are_plain_arithmetic():
+    """a block row per window of records up to the cap"""
+    rows, R = core.regrid_window_rows, core.regrid_record_window()
+    cap = rows(1 << 30)
+    assert 1 < cap <= 65535 and rows(1 << 38) == cap
+    assert rows(1) == rows(R) == 1 and rows(R + 1) == 2
+    for nwin in (2, 1000, cap - 1, cap):
+        assert rows(R * nwin) == nwin and rows(R * (nwin - 1) + 1) == nwin
+    assert rows(R * cap + 1) == rows(R * cap + R + 1) == cap
+    assert rows(0) == 0 and rows(-5) == 0 and rows((1 << 38) + 1) == 0
+    assert _lib.load_regrid().mlx_regrid_window_rows(R * cap + 1) == cap
 
 
 F = 1 << 20

@@ -19,8 +19,8 @@ from momlevel_amd.labeled import DataArray, Dataset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "momlevel_smooth.h")
-NAMES = ["mlx_smooth_apply", "mlx_smooth_max_window", "mlx_smooth_record_window",
-         "mlx_smooth_tile_h", "mlx_smooth_tile_w"]
+NAMES = ["mlx_smooth_apply", "mlx_smooth_max_window", "mlx_smooth_record_rows",
+         "mlx_smooth_record_window", "mlx_smooth_tile_h", "mlx_smooth_tile_w", "mlx_smooth_tiled"]
 
 
 # ---- the C ABI ----------------------------------------------------------------------------------
@@ -81,6 +81,38 @@ def test_geometry_queries():
     assert core.smooth_record_window() >= 1
     with pytest.raises(TypeError):
         core.smooth_tile(np.int32)
+
+
+def test_launch_queries_are_plain_arithmetic():
+    """a block row per record up to the cap; the tiled path for windows up to the largest, rows of
+    whole packs and a plane of at least one tile each way -- five conditions, each flipped alone"""
+    rows = core.smooth_record_rows
+    cap = rows(1 << 30)
+    assert 1 < cap <= 65535 and rows(1 << 38) == cap
+    for nrec in (1, 2, 1000, cap - 1, cap):
+        assert rows(nrec) == nrec
+    assert rows(cap + 1) == rows(cap + 3) == cap
+    assert rows(0) == 0 and rows(-5) == 0 and rows((1 << 38) + 1) == 0
+    tiled = core.smooth_tiled
+    th, tw = core.smooth_tile(np.float64)
+    maxw = core.smooth_max_window()
+    assert maxw <= th + 20 and maxw <= tw  # (so that the planes below hold the largest window)
+    ny, nx = th + 20, tw + 4
+    assert tiled(maxw, maxw, ny, nx) == 1 and tiled(1, 1, th, tw) == 1 and tiled(maxw, 1, th, tw) == 1
+    assert tiled(maxw + 1, maxw, ny, nx) == 0              # Wx
+    assert tiled(maxw, maxw + 1, ny, nx) == 0              # Wy
+    assert [tiled(maxw, maxw, ny, nx + d) for d in (1, 2, 3, 4)] == [0, 0, 0, 1]  # whole packs
+    assert tiled(1, 1, th - 1, nx) == 0 and tiled(1, 1, th, nx) == 1  # a tile of rows
+    assert tiled(1, 1, ny, tw - 4) == 0 and tiled(1, 1, ny, tw) == 1  # a tile of columns
+    assert tiled(3, 3, 1, 4) == 0 and tiled(3, 1, 1, 4) == 0
+    # extents that mlx_smooth_apply refuses
+    for Wx, Wy, y, x in ((0, 1, ny, nx), (1, 0, ny, nx), (-1, 1, ny, nx), (1, 1, 0, nx), (1, 1, ny, 0),
+                         (1, 1, -th, nx), (1, 1, ny, -tw), (1, th + 1, th, nx), (tw + 4, 1, ny, tw),
+                         (1, 1, 1 << 20, 1 << 19)):
+        assert tiled(Wx, Wy, y, x) == 0, (Wx, Wy, y, x)
+    assert tiled(1, 1, 1 << 19, 1 << 19) == 1  # (2^38 cells: the largest plane)
+    lib = _lib.load_smooth()
+    assert lib.mlx_smooth_record_rows(cap + 1) == cap and lib.mlx_smooth_tiled(3, 3, th, tw) == 1
 
 
 def smooth_call(lib, **kw):
